@@ -13,11 +13,23 @@ scaling: each rank generates and scans its own DISTINCT full-size shard
 (seed = 42 + rank) so cross-rank key spaces diverge like real per-minute
 shards do; the RCCL merge reduces the union key space.
 
-Default workload: the BASELINE metric's own shape at its stated scale —
-1 B rows, SELECT host,count(*),max(latency) WHERE ts BETWEEN ... GROUP BY
-host (BASELINE.json configs[2], run per-GPU; the BETWEEN selects ~50% of
-row groups). `--workload c1|c3s|c4s` run the other BASELINE shapes at
---rows scale.
+Default workload: the BASELINE metric's own shape — SELECT host,count(*),
+max(latency) WHERE ts BETWEEN ... GROUP BY host (BASELINE.json configs[2],
+run per-GPU; the BETWEEN selects ~50% of row groups). `--workload
+c1|c3s|c4s` run the other BASELINE shapes at --rows scale.
+
+A plain run does only what the headline figure needs: generate the shard
+(once per data dir), build + load the plan, warm up, time the steps, print
+the line. It runs at 100 M rows/GPU so that set-up (datagen + plan build)
+stays within seconds even with few host cores. `--full` adds the legs that take runs of their own (the
+hot-tier repeat query and the CPU-oracle baseline) and defaults to the
+metric's stated 1 B-row scale, as every figure in BASELINE.md/DESIGN.md.
+
+`--dump-outputs DIR` writes the final table the last timed step returned
+(what a caller of plan.execute + DistMerger.step receives) as
+DIR/<name>.npy, one float array per key/aggregate column in row order.
+Shards are seeded (42 + rank), so the same arguments give the same inputs
+and two builds can be compared output for output.
 
 Rank 0 prints ONE JSON line."""
 
@@ -66,6 +78,53 @@ def args_n_files(a):
     return (a.rows + 262_143) // 262_144
 
 
+def host_cpus():
+    """CPUs this process may actually use: the affinity mask, further capped
+    by OMP_NUM_THREADS where a job scheduler sets it (a container quota does
+    not show in os.cpu_count())."""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        n = os.cpu_count() or 8
+    try:
+        n = min(n, int(os.environ["OMP_NUM_THREADS"]))
+    except (KeyError, ValueError):
+        pass
+    return max(n, 1)
+
+
+def dump_outputs(out_dir, rows, query):
+    """Write the final result table column by column as <name>.npy.
+    Numeric columns -> float64 (None -> NaN; counts and the int64 aggregates
+    of the bench workloads are far below 2**53, so exact). String columns ->
+    float32 [n_rows, max_len] of zero-padded UTF-8 bytes (None -> all -1),
+    so a swapped or missing group key shows up as a numeric difference."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    names = []
+    for k, g in enumerate(query.get("group_by", [])):
+        g = g if isinstance(g, str) else "bin_" + g["bin"]
+        names.append(f"key{k}_{g}")
+    for i, a in enumerate(query["select"]):
+        names.append(f"agg{i}_{a['agg']}" + (f"_{a['col']}" if "col" in a else ""))
+    for c, name in enumerate(names):
+        col = [r[c] for r in rows]
+        if any(isinstance(v, str) for v in col):
+            enc = [None if v is None else v.encode() for v in col]
+            width = max((len(b) for b in enc if b is not None), default=0)
+            arr = np.zeros((len(col), width), dtype=np.float32)
+            for r, b in enumerate(enc):
+                if b is None:
+                    arr[r, :] = -1.0
+                else:
+                    arr[r, :len(b)] = np.frombuffer(b, dtype=np.uint8)
+        else:
+            arr = np.array([np.nan if v is None else float(v) for v in col],
+                           dtype=np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def log(msg):
     if int(os.environ.get("RANK", "0")) == 0:
         print(msg, file=sys.stderr, flush=True)
@@ -77,8 +136,15 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="c2s")
-    ap.add_argument("--rows", type=int, default=1_000_000_000,
-                    help="rows per GPU (weak scaling); BASELINE quotes 1B")
+    ap.add_argument("--rows", type=int, default=None,
+                    help="rows per GPU (weak scaling); default 100M, or "
+                    "with --full the 1B that BASELINE quotes")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: "
+                    "the hot-tier repeat query and the CPU-oracle baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result table as "
+                    "DIR/<name>.npy")
     ap.add_argument("--between-ms", type=int, default=0,
                     help="c2s: BETWEEN window width (default ~50%% of range)")
     ap.add_argument("--data-dir", default=None,
@@ -94,6 +160,10 @@ def main():
                     "all cores) instead of the bounded sample — the "
                     "once-per-round measured baseline (BASELINE.md)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.rows is None:
+        args.rows = 1_000_000_000 if args.full else 100_000_000
 
     if args.data_dir is None:
         args.data_dir = os.environ.get("GPUQ_DATA")
@@ -134,8 +204,8 @@ def main():
     n_files = args_n_files(args)
     shard = os.path.join(args.data_dir, f"{args.workload}_{args.rows}_r{rank}")
     stream_dir = os.path.join(shard, "stream")
-    workers = args.gen_workers or max(8, (os.cpu_count() or 8) // world)
-    # cap per-rank host planning threads too (8 ranks x 256 threads thrash)
+    workers = args.gen_workers or max(8, host_cpus() // world)
+    # cap per-rank host planning threads too (8 ranks x all-core threads thrash)
     os.environ.setdefault("GPUQ_HOST_THREADS", str(workers))
     if not os.path.exists(os.path.join(stream_dir, "stream.json")):
         log(f"[bench] generating {args.rows} rows/rank ({n_files} files, "
@@ -267,7 +337,7 @@ def main():
     # peak device memory stays one plan + the hot tier
     plan.close()
     hot_tier = None
-    if not args.skip_hot_tier:
+    if args.full and not args.skip_hot_tier:
 
     # --- hot-tier repeat query: a NEW plan over the same
     # chunks, served from the session cache — no raw re-upload, no LZ4 walk,
@@ -302,7 +372,7 @@ def main():
 
     # --- CPU baseline: the oracle (kind=port) on a bounded sample ---
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.skip_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.skip_cpu_baseline:
         from oracle import query_oracle as qo
         import pyarrow as pa
 
@@ -333,6 +403,9 @@ def main():
                       f"oracle (pyarrow-decode + numpy agg) on {len(sample_files)} "
                       f"files = {sample_rows} rows, {tcb:.1f}s",
         }
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, rows_final, query)
 
     if rank == 0:
         out = {
