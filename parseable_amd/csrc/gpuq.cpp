@@ -333,6 +333,14 @@ struct Partition {
   std::map<int, int32_t*> d_gid;                    // col -> gid array
   std::map<int, int64_t*> d_val;                    // col -> value array
   std::map<int, uint8_t*> d_valid;                  // col -> valid array
+  // footer-proven null-free columns (every chunk of the column in this
+  // partition has null_count == 0): their tasks launch the direct decode
+  // only (mode 2), no k_def_levels / scratch decode / k_expand
+  std::vector<uint8_t> col_null_free;               // by plan col index
+  // fused value-decode + aggregate (gpuq_plan::fused_valagg): the agg
+  // column's dict and PLAIN page ids merged in page order
+  std::vector<int32_t> valagg_ids;
+  int32_t* d_valagg_ids = nullptr;
   int64_t load_ns = 0;
 };
 
@@ -384,6 +392,15 @@ struct gpuq_plan {
   std::vector<std::string> pinned_keys;  // hot-tier entries pinned by this plan
   int64_t m_cache_hit_bytes = 0;
   bool fused_count = false;      // single dict key + count(*)-only + no preds
+  // single key + {count(*), one i64 sum/min/max over a null-free column
+  // nothing else reads}: the value column is aggregated where it is decoded
+  // (k_val_agg) instead of materialised for k_agg_fast
+  bool fused_valagg = false;
+  int valagg_col = -1;           // the aggregated column (index into cols)
+  bool valagg_late = false;      // group count known only at execute (hash /
+                                 // numeric key): the old kernels stay armed
+  int valagg_blocks = 1024;      // persistent grid cap
+  bool exec_dbg = false;         // GPUQ_PLAN_DEBUG at build: log the agg path
   std::mutex mu;
   // metrics
   int64_t m_rows_scanned = 0, m_rows_out = 0, m_kernel_ns = 0, m_exec_ns = 0,
@@ -1799,7 +1816,64 @@ extern "C" gpuq_plan* gpuq_plan_build(
                         !plan->cols[plan->group_cols[0]].numeric_key;
   }
 
+  // footer-proven null-free columns, per partition
+  for (auto& part : plan->parts) {
+    part.col_null_free.assign(plan->cols.size(), 1);
+    for (auto& t : part.chunks)
+      if (t.cm->null_count != 0) part.col_null_free[t.col_idx] = 0;
+  }
+
+  // fused value-decode + aggregate: exactly the shape launch_agg's fast path
+  // takes with two aggregates, over a column that only the aggregate reads
+  // and whose pages are all dict-encoded or PLAIN 8-byte
+  plan->exec_dbg = getenv("GPUQ_PLAN_DEBUG") != nullptr;
+  if (const char* e = getenv("GPUQ_VALAGG_BLOCKS"))
+    plan->valagg_blocks = std::max(1, atoi(e));
+  if (!plan->is_projection && !getenv("GPUQ_NO_FUSED_VALAGG") &&
+      plan->group_cols.size() == 1 && plan->aggs.size() == 2 &&
+      plan->aggs[0].kind == AGGK_COUNT_STAR && plan->n_fsum == 0 &&
+      (plan->aggs[1].kind == AGGK_SUM_I64 || plan->aggs[1].kind == AGGK_MIN_I64 ||
+       plan->aggs[1].kind == AGGK_MAX_I64) &&
+      plan->aggs[1].cnt_is_presence && !plan->needs_cascade) {
+    const int vc = plan->aggs[1].col_idx;
+    const auto& c = plan->cols[vc];
+    const auto& kc = plan->cols[plan->group_cols[0]];
+    bool ok = c.phys == PT_INT64 && !c.is_bin && !c.hash_mode &&
+              !c.numeric_key && !c.need_gid && !c.need_rank &&
+              c.cmp_preds.empty() && c.lut_preds.empty() &&
+              plan->group_cols[0] != vc;
+    for (auto& o : plan->cols) ok &= !(o.is_bin && o.bin_src == vc);
+    const bool late = kc.hash_mode || kc.numeric_key;
+    if (!late) ok &= (int64_t)plan->n_groups * 16 <= 64 * 1024;
+    for (auto& part : plan->parts) {
+      if (!ok) break;
+      for (auto& kv : part.tasks) {
+        if (kv.first.second != vc) continue;
+        if (kv.first.first != TK_DICT_VAL && kv.first.first != TK_PLAIN_VAL)
+          ok = false;  // delta-encoded (or any other) pages: old path
+      }
+    }
+    if (ok) {
+      plan->fused_valagg = true;
+      plan->valagg_col = vc;
+      plan->valagg_late = late;
+      for (auto& part : plan->parts) {
+        for (int k : {TK_DICT_VAL, TK_PLAIN_VAL}) {
+          auto it = part.tasks.find({k, vc});
+          if (it != part.tasks.end())
+            part.valagg_ids.insert(part.valagg_ids.end(), it->second.begin(),
+                                   it->second.end());
+        }
+        std::sort(part.valagg_ids.begin(), part.valagg_ids.end());
+      }
+    }
+  }
+
   if (getenv("GPUQ_PLAN_DEBUG")) {
+    fprintf(stderr, "[gpuq plan] fused_count=%d fused_valagg=%d%s\n",
+            (int)plan->fused_count, (int)plan->fused_valagg,
+            plan->fused_valagg && plan->valagg_late
+                ? " (group count checked at execute)" : "");
     for (size_t p = 0; p < plan->parts.size(); p++) {
       const auto& pt = plan->parts[p];
       fprintf(stderr,
@@ -1931,6 +2005,9 @@ extern "C" int32_t gpuq_plan_load(gpuq_plan* plan, int32_t pi) try {
     upload_pool(kv.second.data(), kv.second.size() * 4, (void**)&d);
     part.d_ids[kv.first] = d;
   }
+  if (plan->fused_valagg)
+    upload_pool(part.valagg_ids.data(), part.valagg_ids.size() * 4,
+                (void**)&part.d_valagg_ids);
   // column outputs
   for (size_t ci = 0; ci < plan->cols.size(); ci++) {
     auto& c = plan->cols[ci];
@@ -1947,6 +2024,10 @@ extern "C" int32_t gpuq_plan_load(gpuq_plan* plan, int32_t pi) try {
         part.d_valid[(int)ci] = v;
       }
     }
+    // the fused path never materialises its value column (9 B/row of HBM),
+    // unless the execute-time group-count check can still fall back
+    if (plan->fused_valagg && !plan->valagg_late && (int)ci == plan->valagg_col)
+      continue;
     if (c.need_val) {
       int64_t* d; HIP_TRY(hipMalloc(&d, std::max<int64_t>(part.n_rows * 8, 16)));
       part.d_val[(int)ci] = d;
@@ -2570,10 +2651,45 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
                         plan->n_groups, (int)plan->aggs.size(), part.d_err);
     HIP_TRY(hipEventRecord(ev1, st));
   } else {
-  for (auto& kv : part.tasks) {
+  auto run_task = [&](const std::pair<const std::pair<int, int>,
+                                      std::vector<int32_t>>& kv) {
     int kind = kv.first.first, col = kv.first.second;
     int n = (int)kv.second.size();
     int32_t* ids = part.d_ids[kv.first];
+    // footer-proven null-free column: the direct decode alone, validity
+    // asserted (mode 2) — the def-level pass, the scratch decode and the
+    // expansion would each find nothing to do
+    if (part.col_null_free[col]) {
+      switch (kind) {
+        case TK_DICT_GID: {
+          auto it = part.d_valid.find(col);
+          launch_dict_gid(st, part.d_dec, part.d_pages, ids, n, part.d_remap,
+                          part.d_gid[col],
+                          it != part.d_valid.end() ? it->second : nullptr,
+                          nullptr, 2, part.d_err);
+          return;
+        }
+        case TK_DICT_VAL:
+          launch_dict_i64(st, part.d_dec, part.d_pages, ids, n, part.d_dictv,
+                          part.d_val[col], part.d_valid[col], nullptr, 2,
+                          part.d_err);
+          return;
+        case TK_PLAIN_VAL:
+          launch_plain_fixed(st, part.d_dec, part.d_pages, ids, n,
+                             part.d_val[col], part.d_valid[col], nullptr, 2,
+                             part.d_err);
+          return;
+        case TK_POOL_VAL:
+          launch_pool_vals(st, part.d_dec, part.d_pages, ids, n, part.d_dictv,
+                           part.d_val[col], part.d_valid[col], nullptr, 2);
+          return;
+        case TK_DICT_MASK:
+          launch_dict_mask(st, part.d_dec, part.d_pages, ids, n, part.d_lut,
+                           part.d_mask, 2, part.d_err);
+          return;
+        default: break;  // delta has one launch already; contains needs rowof
+      }
+    }
     switch (kind) {
       case TK_DICT_GID: {
         auto it = part.d_valid.find(col);
@@ -2640,7 +2756,7 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
                           part.d_tmpvalid, nullptr, nullptr,
                           part.d_rank, part.d_present, part.d_err);
         launch_dict_mask(st, part.d_dec, part.d_pages, ids, n, part.d_lut,
-                         part.d_mask, part.d_err);
+                         part.d_mask, 0, part.d_err);
         launch_dict_lut_scr(st, part.d_dec, part.d_pages, ids, n, part.d_lut,
                             part.d_scr, part.d_present, part.d_err);
         launch_expand(st, part.d_dec, part.d_pages, ids, n, part.d_scr,
@@ -2664,6 +2780,11 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
         break;
       }
     }
+  };
+  for (auto& kv : part.tasks) {
+    // the fused path aggregates this column where it decodes it (step 3)
+    if (plan->fused_valagg && kv.first.second == plan->valagg_col) continue;
+    run_task(kv);
   }
   // raw-byte utf8: device hash build assigns dense gids per hash-mode
   // group key (one shared table, rebuilt per column); string predicates
@@ -2856,7 +2977,25 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
   if (plan->n_fsum)
     HIP_TRY(hipMemsetAsync(part.d_fsum, 0,
                            (size_t)plan->n_fsum * n_groups_exec * 4 * 8, st));
-  launch_agg(st, a);
+  // masks and key gids are final here: the fused kernel decodes the value
+  // column straight into the table, unless a hash/numeric key produced more
+  // groups than its LDS table holds — then the column is materialised now
+  // and the old kernels run
+  bool fused = plan->fused_valagg && n_groups_exec * 16 <= 64 * 1024;
+  if (plan->fused_valagg && plan->exec_dbg)
+    fprintf(stderr, "[gpuq exec] part %d: valagg=%s n_groups=%lld\n", pi,
+            fused ? "fused" : "fallback", (long long)n_groups_exec);
+  if (fused) {
+    launch_val_agg(st, part.d_dec, part.d_pages, part.d_valagg_ids,
+                   (int)part.valagg_ids.size(), part.d_dictv, a.key_gid[0],
+                   a.mask, part.d_table, (int32_t)n_groups_exec, a.n_aggs,
+                   plan->aggs[1].kind, plan->valagg_blocks, part.d_err);
+  } else {
+    if (plan->fused_valagg)
+      for (auto& kv : part.tasks)
+        if (kv.first.second == plan->valagg_col) run_task(kv);
+    launch_agg(st, a);
+  }
   HIP_TRY(hipEventRecord(ev1, st));
   }  // !fused_count
 
@@ -3301,6 +3440,7 @@ gpuq_plan::~gpuq_plan() {
     F(part.d_keys); F(part.d_keys_sorted); F(part.d_rows);
     F(part.d_rows_sorted); F(part.d_count); F(part.d_sort_temp);
     for (auto& kv : part.d_ids) F(kv.second);
+    F(part.d_valagg_ids);
     for (auto& kv : part.d_gid) F(kv.second);
     for (auto& kv : part.d_val) F(kv.second);
     for (auto& kv : part.d_valid) F(kv.second);

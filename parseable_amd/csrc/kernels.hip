@@ -638,11 +638,21 @@ struct EmitDictMask {
 // the dense stream to scratch at [row0+k]; a separate expansion kernel
 // then writes the final arrays COALESCED through the k_def_levels rank map
 // (a scatter here would cost a read-modify-write line fetch per value).
+// mode 2 (FOOTER): the column's chunk footers prove null_count == 0 — every
+// page decodes direct without consulting the all_valid probe (which only
+// recognises a single RLE run); def_levels() still supplies the value-stream
+// offset. No k_def_levels / scratch / k_expand launches accompany it.
 // Workgroups carry DP_WAVES waves per page: every wave walks the (cheap,
 // lane-redundant) run headers, but runs are unpacked round-robin by wave —
 // at 1 B-row scale a page-per-wave launch was ~1.9k waves, far too few to
 // hide latency on the unpack loads.
 #define DP_WAVES 4
+// Emitters whose per-value work is a chain of dependent loads (packed index
+// -> gather) with no store between them can declare BATCH > 1: the unpack
+// loop then issues BATCH values' index loads, then their gathers
+// (Emit::fetch), then applies them (Emit::apply) — the loads of one batch
+// are in flight together instead of one round trip per value.
+template <class Emit> struct EmitBatch { static constexpr int N = 1; };
 template <class Emit>
 __device__ void dict_page_decode(const DevPage& pg, const uint8_t* payload, Emit emit,
                                  const uint32_t* __restrict__ present,
@@ -655,10 +665,10 @@ __device__ void dict_page_decode(const DevPage& pg, const uint8_t* payload, Emit
   const uint32_t row0 = pg.row_start;
   if (mode == 0) {
     if (!all_valid) return;
-  } else {
+  } else if (mode == 1) {
     if (all_valid) return;
     nv = present[page_id];
-  }
+  }  // mode 2: every value present (footer), whatever shape the def runs take
 
   {
     int bw = *vals++;
@@ -692,12 +702,11 @@ __device__ void dict_page_decode(const DevPage& pg, const uint8_t* payload, Emit
         // reads (8 lanes share a group) stay in L1/L2.
         uint32_t run_vals = groups * 8;
         if (run_vals > nv - v) run_vals = nv - v;
-        if ((rc++ % DP_WAVES) == (uint32_t)wave)
-        for (uint32_t i = lane; i < run_vals; i += WAVE) {
+        const uint32_t mask_v = (bw >= 32) ? 0xffffffffu : ((1u << bw) - 1);
+        auto unpack = [&](uint32_t i) -> uint32_t {
           uint32_t g = i >> 3;
           int k = (int)(i & 7);
           const uint8_t* q = p + (size_t)g * bw;
-          uint32_t mask_v = (bw >= 32) ? 0xffffffffu : ((1u << bw) - 1);
           // one unaligned 8B load replaces the byte loop: bits beyond the
           // group's bw bytes are never selected (k*bw+bw <= 64 => the used
           // window lies inside q[0..8)); arena padding covers the over-read
@@ -711,8 +720,47 @@ __device__ void dict_page_decode(const DevPage& pg, const uint8_t* payload, Emit
             __builtin_memcpy(&acc2, q + (k * bw) / 8, 8);
             idx = (uint32_t)(acc2 >> ((k * bw) % 8)) & mask_v;
           }
-          if (idx >= dict_n) { atomicExch(d_error, ERR_DICT_RANGE); idx = 0; }
-          emit(target(v + i), idx);
+          return idx;
+        };
+        if ((rc++ % DP_WAVES) == (uint32_t)wave) {
+          if constexpr (EmitBatch<Emit>::N > 1) {
+            constexpr int NB = EmitBatch<Emit>::N;
+            // branch-free: lanes past the run's end re-read its last value
+            // (in bounds) and are switched off only at apply, so the NB
+            // loads of each phase issue back to back. Value i starts at bit
+            // i*bw of the run (groups are contiguous); one unaligned 8 B
+            // load covers it for every bw <= 32.
+            for (uint32_t i0 = lane; i0 < run_vals; i0 += WAVE * NB) {
+              uint32_t ic[NB], idx[NB];
+              uint64_t acc[NB];
+#pragma unroll
+              for (int u = 0; u < NB; u++) {
+                uint32_t i = i0 + u * WAVE;
+                ic[u] = i < run_vals ? i : run_vals - 1;
+                __builtin_memcpy(&acc[u], p + (((size_t)ic[u] * bw) >> 3), 8);
+              }
+              bool bad = false;
+#pragma unroll
+              for (int u = 0; u < NB; u++) {
+                idx[u] = (uint32_t)(acc[u] >> ((ic[u] * (uint32_t)bw) & 7)) & mask_v;
+                if (idx[u] >= dict_n) { bad = true; idx[u] = 0; }
+              }
+              if (bad) atomicExch(d_error, ERR_DICT_RANGE);
+              typename Emit::Pending pend[NB];
+#pragma unroll
+              for (int u = 0; u < NB; u++)
+                pend[u] = emit.fetch(target(v + ic[u]), idx[u],
+                                     i0 + u * WAVE < run_vals);
+#pragma unroll
+              for (int u = 0; u < NB; u++) emit.apply(pend[u]);
+            }
+          } else {
+            for (uint32_t i = lane; i < run_vals; i += WAVE) {
+              uint32_t idx = unpack(i);
+              if (idx >= dict_n) { atomicExch(d_error, ERR_DICT_RANGE); idx = 0; }
+              emit(target(v + i), idx);
+            }
+          }
         }
         p += (size_t)groups * bw;
         uint32_t add = groups * 8;
@@ -898,8 +946,8 @@ k_plain_fixed(const uint8_t* __restrict__ dec, const DevPage* __restrict__ pages
   const uint8_t* def_start; uint32_t def_len; bool all_valid;
   const uint8_t* vals = def_levels(pg, dec + pg.dst_off, &def_start, &def_len, &all_valid);
   const uint32_t row0 = pg.row_start;
-  if (mode == 0) {
-    if (!all_valid) return;
+  if (mode == 0 || mode == 2) {
+    if (mode == 0 && !all_valid) return;
     uint32_t nv = pg.num_values;
     for (uint32_t i = lane; i < nv; i += WAVE) {
       int64_t v;
@@ -979,8 +1027,8 @@ k_pool_vals(const uint8_t* __restrict__ dec, const DevPage* __restrict__ pages,
   def_levels(pg, dec + pg.dst_off, &def_start, &def_len, &all_valid);
   const uint32_t row0 = pg.row_start;
   const int64_t* src = pool + pg.aux_val;
-  if (mode == 0) {
-    if (!all_valid) return;
+  if (mode == 0 || mode == 2) {
+    if (mode == 0 && !all_valid) return;
     for (uint32_t i = lane; i < pg.num_values; i += WAVE) {
       out[row0 + i] = src[i];
       if (valid) valid[row0 + i] = 1;
@@ -2161,6 +2209,122 @@ k_agg_fast(AggArgs a) {
   }
 }
 
+// ------------------------------------------------------------------
+// FUSED value-decode + aggregate: ONE key, {COUNT_STAR, one i64 sum/min/max
+// over a footer-proven null-free column that nothing else reads}. The value
+// column's dict and PLAIN pages are decoded straight into a per-block LDS
+// table {count, value} per group, indexed by the already-final gid[row]
+// (and gated by mask[row] where a selection mask exists): the row-aligned
+// value/valid arrays are never written nor read back, and k_agg_fast's pass
+// over gid/value/mask disappears. Persistent blocks stride over the pages so
+// the table is initialised and flushed once per block; the flush merges into
+// table slots 0 (presence) and 3 (agg 1's value) exactly as k_agg_fast does.
+// All int64 updates are exact and order-independent, so results are
+// bit-identical to the materialise-then-aggregate path.
+// ------------------------------------------------------------------
+template <int K1>
+__device__ inline void valagg_update(uint64_t* lt, int32_t g, int64_t v) {
+  atomicAdd((unsigned long long*)&lt[2 * g], 1ull);
+  if (K1 == AGGK_SUM_I64)
+    atomicAdd((unsigned long long*)&lt[2 * g + 1], (unsigned long long)v);
+  else if (K1 == AGGK_MIN_I64) atomic_min_i64(&lt[2 * g + 1], v);
+  else atomic_max_i64(&lt[2 * g + 1], v);
+}
+template <int K1, bool MASK>
+struct EmitValAgg {
+  const int64_t* dictv;
+  const int32_t* gid;
+  const uint8_t* mask;   // selection mask, read only when MASK
+  uint64_t* lt;
+  __device__ void operator()(uint32_t row, uint32_t idx) const {
+    if (MASK && !mask[row]) return;
+    valagg_update<K1>(lt, gid[row], dictv[idx]);
+  }
+  // batched form (EmitBatch): all loads of a batch first, LDS updates after
+  struct Pending { int64_t v; int32_t g; uint8_t m; bool on; };
+  __device__ Pending fetch(uint32_t row, uint32_t idx, bool live) const {
+    Pending p;  // row and idx are in bounds also for !live (clamped)
+    p.g = gid[row];
+    p.v = dictv[idx];
+    p.m = MASK ? mask[row] : (uint8_t)1;
+    p.on = live;
+    return p;
+  }
+  __device__ void apply(const Pending& p) const {
+    if (p.on && p.m) valagg_update<K1>(lt, p.g, p.v);
+  }
+};
+#define VALAGG_BATCH 4
+template <int K1, bool MASK> struct EmitBatch<EmitValAgg<K1, MASK>> {
+  static constexpr int N = VALAGG_BATCH;
+};
+
+template <int K1, bool MASK>
+__global__ void __launch_bounds__(WAVE * DP_WAVES)
+k_val_agg(const uint8_t* __restrict__ dec, const DevPage* __restrict__ pages,
+          const int32_t* __restrict__ ids, int n,
+          const int64_t* __restrict__ dictv_pool,
+          const int32_t* __restrict__ gid, const uint8_t* __restrict__ mask,
+          uint64_t* __restrict__ table, int32_t n_groups, int slots,
+          int32_t* d_error) {
+  extern __shared__ uint64_t lt[];   // n_groups x {count, value}
+  const uint64_t vinit = K1 == AGGK_MIN_I64 ? (uint64_t)INT64_MAX
+                         : K1 == AGGK_MAX_I64 ? (uint64_t)INT64_MIN : 0ull;
+  for (int i = threadIdx.x; i < 2 * n_groups; i += blockDim.x)
+    lt[i] = (i & 1) ? vinit : 0ull;
+  __syncthreads();
+
+  for (int pi = blockIdx.x; pi < n; pi += gridDim.x) {
+    const DevPage pg = pages[ids[pi]];
+    const uint8_t* payload = dec + pg.dst_off;
+    if (pg.encoding == ENC_PLAIN) {
+      // footer says null-free: exactly num_values 8-byte values follow the
+      // def-level block, however its runs are encoded
+      uint32_t skip = 0;
+      if (pg.optional) { memcpy(&skip, payload, 4); skip += 4; }
+      const uint32_t nv = pg.num_values, row0 = pg.row_start;
+      if ((uint64_t)skip + (uint64_t)nv * 8 > pg.uncomp_size) {
+        if (threadIdx.x == 0) atomicExch(d_error, ERR_PAGE);
+        continue;
+      }
+      const uint8_t* vals = payload + skip;
+      for (uint32_t i0 = threadIdx.x; i0 < nv; i0 += blockDim.x * VALAGG_BATCH) {
+        int64_t v[VALAGG_BATCH];
+        int32_t g[VALAGG_BATCH];
+        uint8_t m[VALAGG_BATCH];
+        bool on[VALAGG_BATCH];
+#pragma unroll
+        for (int u = 0; u < VALAGG_BATCH; u++) {
+          uint32_t i = i0 + u * blockDim.x;
+          on[u] = i < nv;
+          uint32_t row = row0 + (on[u] ? i : i0);
+          __builtin_memcpy(&v[u], vals + (size_t)(on[u] ? i : i0) * 8, 8);
+          g[u] = gid[row];
+          m[u] = MASK ? mask[row] : (uint8_t)1;
+        }
+#pragma unroll
+        for (int u = 0; u < VALAGG_BATCH; u++)
+          if (on[u] && m[u]) valagg_update<K1>(lt, g[u], v[u]);
+      }
+    } else {
+      EmitValAgg<K1, MASK> e{dictv_pool + pg.aux_val, gid, mask, lt};
+      dict_page_decode(pg, payload, e, (const uint32_t*)nullptr, ids[pi], 2,
+                       d_error);
+    }
+  }
+  __syncthreads();
+  for (int g = threadIdx.x; g < n_groups; g += blockDim.x) {
+    uint64_t c = lt[2 * g];
+    if (!c) continue;
+    uint64_t* row = table + (int64_t)g * slots;
+    atomicAdd((unsigned long long*)&row[0], (unsigned long long)c);
+    uint64_t v = lt[2 * g + 1];
+    if (K1 == AGGK_SUM_I64) atomicAdd((unsigned long long*)&row[3], (unsigned long long)v);
+    else if (K1 == AGGK_MIN_I64) atomic_min_i64(&row[3], (int64_t)v);
+    else atomic_max_i64(&row[3], (int64_t)v);
+  }
+}
+
 __global__ void k_init_table(uint64_t* table, int32_t n_groups, int n_aggs,
                              const int32_t* agg_kind) {
   int slots = 1 + 2 * n_aggs;
@@ -2243,10 +2407,10 @@ void launch_dict_i64(hipStream_t st, const uint8_t* dec, const DevPage* pages,
 }
 void launch_dict_mask(hipStream_t st, const uint8_t* dec, const DevPage* pages,
                       const int32_t* ids, int n, const uint8_t* lut_pool,
-                      uint8_t* mask, int32_t* d_err) {
+                      uint8_t* mask, int mode, int32_t* d_err) {
   if (!n) return;
   EmitDictMaskP e{}; e.pool = lut_pool; e.mask = mask;
-  hipLaunchKernelGGL(k_dict_pages<EmitDictMaskP>, dim3(n), dim3(WAVE * DP_WAVES), 0, st, dec, pages, ids, n, e, (const uint32_t*)nullptr, 0, d_err);
+  hipLaunchKernelGGL(k_dict_pages<EmitDictMaskP>, dim3(n), dim3(WAVE * DP_WAVES), 0, st, dec, pages, ids, n, e, (const uint32_t*)nullptr, mode, d_err);
 }
 void launch_dict_lut_scr(hipStream_t st, const uint8_t* dec,
                          const DevPage* pages, const int32_t* ids, int n,
@@ -2325,6 +2489,39 @@ void launch_dict_count(hipStream_t st, const uint8_t* dec, const DevPage* pages,
   size_t lds = (size_t)n_groups * 8;
   hipLaunchKernelGGL(k_dict_count, dim3(blocks), dim3(WAVE), lds, st,
                      dec, pages, ids, n, remap_pool, table, n_groups, n_aggs, d_err);
+}
+
+void launch_val_agg(hipStream_t st, const uint8_t* dec, const DevPage* pages,
+                    const int32_t* ids, int n, const int64_t* dictv_pool,
+                    const int32_t* gid, const uint8_t* mask, uint64_t* table,
+                    int32_t n_groups, int n_aggs, int kind, int max_blocks,
+                    int32_t* d_err) {
+  if (!n) return;
+  // even page counts per persistent block: with n just above the cap a
+  // plain min(n, cap) grid leaves half the blocks one page short
+  if (max_blocks < 1) max_blocks = 1;
+  int per = (n + max_blocks - 1) / max_blocks;
+  int blocks = (n + per - 1) / per;
+  size_t lds = (size_t)n_groups * 16;
+  int slots = 1 + 2 * n_aggs;
+  auto launch = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(WAVE * DP_WAVES), lds, st, dec,
+                       pages, ids, n, dictv_pool, gid, mask, table, n_groups,
+                       slots, d_err);
+  };
+  if (mask) {
+    switch (kind) {
+      case AGGK_SUM_I64: launch(k_val_agg<AGGK_SUM_I64, true>); break;
+      case AGGK_MIN_I64: launch(k_val_agg<AGGK_MIN_I64, true>); break;
+      default: launch(k_val_agg<AGGK_MAX_I64, true>); break;
+    }
+  } else {
+    switch (kind) {
+      case AGGK_SUM_I64: launch(k_val_agg<AGGK_SUM_I64, false>); break;
+      case AGGK_MIN_I64: launch(k_val_agg<AGGK_MIN_I64, false>); break;
+      default: launch(k_val_agg<AGGK_MAX_I64, false>); break;
+    }
+  }
 }
 
 void launch_agg(hipStream_t st, const AggArgs& a) {

@@ -36,7 +36,7 @@ void launch_dict_i64(hipStream_t, const uint8_t* dec, const DevPage*,
                      int mode, int32_t* d_err);
 void launch_dict_mask(hipStream_t, const uint8_t* dec, const DevPage*,
                       const int32_t* ids, int n, const uint8_t* lut_pool,
-                      uint8_t* mask, int32_t* d_err);
+                      uint8_t* mask, int mode, int32_t* d_err);
 void launch_dict_lut_scr(hipStream_t, const uint8_t* dec, const DevPage*,
                          const int32_t* ids, int n, const uint8_t* lut_pool,
                          uint8_t* scr, const uint32_t* present, int32_t* d_err);
@@ -62,6 +62,13 @@ void launch_dict_count(hipStream_t, const uint8_t* dec, const DevPage*,
                        const int32_t* ids, int n, const int32_t* remap_pool,
                        uint64_t* table, int32_t n_groups, int n_aggs,
                        int32_t* d_err);
+// fused value decode + aggregate (kernels.hip k_val_agg): ids lists the agg
+// column's dict AND PLAIN data pages; kind is AGGK_SUM/MIN/MAX_I64
+void launch_val_agg(hipStream_t, const uint8_t* dec, const DevPage*,
+                    const int32_t* ids, int n, const int64_t* dictv_pool,
+                    const int32_t* gid, const uint8_t* mask, uint64_t* table,
+                    int32_t n_groups, int n_aggs, int kind, int max_blocks,
+                    int32_t* d_err);
 void launch_agg(hipStream_t, const AggArgs&);
 void launch_pool_vals(hipStream_t, const uint8_t* dec, const DevPage*,
                       const int32_t* ids, int n, const int64_t* pool,
