@@ -98,6 +98,99 @@ def _msg_col(rng, n):
         pa.py_buffer(chars.tobytes()))
 
 
+C6_LEVELS = ["ERROR", "Error", "error", "WARN", "Warn", "warn",
+             "INFO", "Info", "info", "DEBUG", "Debug", "debug"]
+C6_TOKENS = ["Error", "ERROR", "error", "eRrOr", "TIMEOUT", "timeout"]
+# filler vocabulary: ASCII of both cases plus multi-byte UTF-8 (no U+212A /
+# U+017F, whose Unicode case mapping lands in ASCII). No word contains a
+# C6_TOKENS entry under ASCII case folding.
+C6_WORDS = ["request", "Served", "retry", "from", "cache", "Zone", "queue",
+            "user", "path", "GET", "put", "ok", "a", "b7", "x", "é", "É",
+            "日本", "café", "État", "node", "disk", "full", "slow", "r"]
+C6_BIG_LEN = 40_000
+
+
+def _c6_filler(rng, nbytes):
+    """Space-joined C6_WORDS of at most nbytes UTF-8 bytes (whole words)."""
+    out, used = [], 0
+    while True:
+        w = C6_WORDS[int(rng.integers(0, len(C6_WORDS)))]
+        add = len(w.encode()) + (1 if out else 0)
+        if used + add > nbytes:
+            break
+        out.append(w)
+        used += add
+    return " ".join(out)
+
+
+def _c6_batch(rng, n, minute, cols):
+    """String-predicate stress (LIKE family + IS [NOT] NULL): mixed-case
+    tokens at the start / middle / very end of `message` values, values equal
+    to a token, values shorter than any token (empty included) right after
+    values that end in a token, lengths 0-200 B (so u32 length prefixes with
+    a byte in 'A'..'Z', 65-90, occur), multi-byte filler; `level` stays
+    dict-encoded, `message` and `tag` overflow the 4 KiB dictionary limit
+    into PLAIN pages; `latency` is a REQUIRED column; `sparse` is all-NULL in
+    odd minutes and null-free in even ones; minute 0 carries one 40,000-byte
+    message (Error ... TIMEOUT)."""
+    cols["latency"] = pa.array(
+        rng.integers(0, 10**6, n, dtype=np.int64), type=pa.int64())
+    lv_idx = rng.integers(0, len(C6_LEVELS), n).astype(np.int32)
+    lv = pa.DictionaryArray.from_arrays(
+        pa.array(lv_idx, mask=rng.random(n) < 0.10), pa.array(C6_LEVELS))
+    cols["level"] = lv.cast(pa.string())
+
+    kind = rng.random(n)
+    msgs = []
+    for i in range(n):
+        k = kind[i]
+        tok = C6_TOKENS[int(rng.integers(0, len(C6_TOKENS)))]
+        if k < 0.25:
+            msgs.append(None)
+        elif k < 0.30:
+            msgs.append(tok)                                   # exactly a token
+        elif k < 0.36:
+            msgs.append(["", "a", "Er", "TIME", "rr"][int(rng.integers(0, 5))])
+        elif k < 0.46:
+            msgs.append(tok + " " + _c6_filler(rng, int(rng.integers(0, 190))))
+        elif k < 0.56:
+            msgs.append(_c6_filler(rng, int(rng.integers(1, 190))) + " " + tok)
+        elif k < 0.66:
+            msgs.append(_c6_filler(rng, int(rng.integers(1, 95))) + " " + tok
+                        + " " + _c6_filler(rng, int(rng.integers(1, 95))))
+        else:
+            msgs.append(_c6_filler(rng, int(rng.integers(0, 201))))
+    # a too-short value directly after one that ends in a token: a suffix
+    # compare that formed its address before checking the length would read
+    # the neighbour's tail
+    for j in range(7, n - 1, 97):
+        msgs[j] = _c6_filler(rng, 30) + " " + C6_TOKENS[(j // 97) % len(C6_TOKENS)]
+        msgs[j + 1] = ["", "ut", "or"][(j // 97) % 3]
+    if minute == 0 and n > 2:
+        big = "Error " + _c6_filler(rng, C6_BIG_LEN - 100) + " "
+        big = big + "x" * (C6_BIG_LEN - len(big.encode()) - 7) + "TIMEOUT"
+        msgs[n // 2] = big
+    cols["message"] = pa.array(msgs, type=pa.string())
+
+    tagn = rng.integers(0, 500, n)
+    tagp = rng.integers(0, 3, n)
+    tnull = rng.random(n) < 0.30
+    cols["tag"] = pa.array(
+        [None if m else f"{('Tag', 'tag', 'TAG')[p]}-{v:06d}"
+         for m, p, v in zip(tnull, tagp, tagn)], type=pa.string())
+    cols["opt_i64"] = pa.array(rng.integers(-10**9, 10**9, n, dtype=np.int64),
+                               mask=rng.random(n) < 0.50)
+    if minute % 2:
+        cols["sparse"] = pa.array([None] * n, type=pa.string())
+    else:
+        cols["sparse"] = pa.array(
+            [f"sp-{v}" for v in rng.integers(0, 40, n)], type=pa.string())
+    tbl = pa.table(cols)
+    fields = [f.with_nullable(False) if f.name == "latency" else f
+              for f in tbl.schema]
+    return tbl.cast(pa.schema(fields))
+
+
 def _minute_batch(config: str, rng: np.random.Generator, n: int, minute: int):
     """One file's rows. Timestamps descending within the minute
     (src/parseable/streams.rs:756-760: SortingColumn time DESC)."""
@@ -155,6 +248,8 @@ def _minute_batch(config: str, rng: np.random.Generator, n: int, minute: int):
         tagv = rng.integers(0, 800, n)
         cols["opt_tag"] = pa.array(
             [None if m else f"tag-{v:06d}" for m, v in zip(mask, tagv)])
+    elif config == "c6":
+        return _c6_batch(rng, n, minute, cols)
     elif config == "c4":
         # OTel-shaped: 3 group keys + 61 sparse attribute columns, 50-90% null
         cols["service"] = _dict_col(rng, n, [f"svc-{i}" for i in range(30)])
@@ -296,7 +391,7 @@ def _gen_file_inner(root, stream, config, rows, seed, rows_per_file,
         kw = {}
         if data_page_size:
             kw["data_page_size"] = data_page_size
-        if config == "c5":
+        if config in ("c5", "c6"):
             # force dict-page overflow -> PLAIN fallback mid-chunk
             kw["dictionary_pagesize_limit"] = 4096
         ts_idx = tbl.schema.get_field_index("p_timestamp")

@@ -82,7 +82,43 @@ typedef enum {
   GPUQ_BETWEEN,       /* lo <= x <= hi (SQL BETWEEN); with hi_exclusive:
                          lo <= x < hi — the injected time filter shape of
                          query/mod.rs:829-888 */
-  GPUQ_CONTAINS       /* LIKE '%lit%' byte substring */
+  GPUQ_CONTAINS,      /* LIKE '%lit%' byte substring
+                         (WhereConfigOperator::Contains,
+                         alerts/alerts_utils.rs:620-622) */
+  /* The rest of the filter builder's operator set (scalar_condition_expr,
+   * alerts/alerts_utils.rs:612-640; condition_to_expr :426-441).
+   * Semantics shared by the seven string ops:
+   *  - the literal is the already-unescaped byte string: '%' and '_' in it
+   *    are ordinary bytes (the caller strips ESCAPE '\' and the leading /
+   *    trailing '%');
+   *  - a NULL row satisfies none of them, the negated ones included (NOT
+   *    LIKE on NULL is NULL, the row is dropped) — only IS_NULL selects
+   *    NULL rows;
+   *  - an empty literal: the positive ops match every non-null row, the
+   *    negated ops match no row;
+   *  - the column must be utf8 and the literal GPUQ_LIT_STR, anything else
+   *    is a plan-build error;
+   *  - none of them prunes a file or a row group by min/max statistics. */
+  GPUQ_ICONTAINS = 8, /* ILIKE '%lit%' (alerts_utils.rs:626-628). ASCII
+                         case-insensitive: bytes 'A'-'Z' fold to 'a'-'z' on
+                         both sides, every other byte compares exactly. A
+                         literal holding a byte >= 0x80 is rejected at plan
+                         build; haystack bytes >= 0x80 are never folded
+                         (differs from Unicode ILIKE for U+212A and U+017F
+                         only) */
+  GPUQ_STARTS_WITH,   /* LIKE 'lit%'        (alerts_utils.rs:629-631) */
+  GPUQ_ENDS_WITH,     /* LIKE '%lit'        (alerts_utils.rs:635-637) */
+  GPUQ_NOT_CONTAINS,  /* NOT LIKE '%lit%'   (alerts_utils.rs:623-625) */
+  GPUQ_NOT_ICONTAINS, /* NOT ILIKE '%lit%'  (negation of :626-628; same
+                         folding rule as GPUQ_ICONTAINS) */
+  GPUQ_NOT_STARTS_WITH, /* NOT LIKE 'lit%'  (alerts_utils.rs:632-634) */
+  GPUQ_NOT_ENDS_WITH, /* NOT LIKE '%lit'    (alerts_utils.rs:638-640) */
+  GPUQ_IS_NULL,       /* col IS NULL (alerts_utils.rs:428-440). No literal:
+                         lit_kind/str/i64/f64 are ignored. Any decodable
+                         column type (utf8, i64, i32, f64, timestamp); on a
+                         required column it selects nothing */
+  GPUQ_IS_NOT_NULL    /* col IS NOT NULL (alerts_utils.rs:428-440); a no-op
+                         on a required column */
 } gpuq_op;
 
 typedef enum { GPUQ_LIT_I64 = 0, GPUQ_LIT_F64, GPUQ_LIT_STR } gpuq_lit;

@@ -52,7 +52,14 @@ class GpuqMetrics(C.Structure):
     ]
 
 
-OPS = {"eq": 0, "ne": 1, "lt": 2, "le": 3, "gt": 4, "ge": 5, "between": 6, "contains": 7}
+OPS = {"eq": 0, "ne": 1, "lt": 2, "le": 3, "gt": 4, "ge": 5, "between": 6, "contains": 7,
+       "icontains": 8, "starts_with": 9, "ends_with": 10, "not_contains": 11,
+       "not_icontains": 12, "not_starts_with": 13, "not_ends_with": 14,
+       "is_null": 15, "is_not_null": 16}
+# the LIKE-family string ops and the literal-free null ops (include/gpuq.h)
+STR_OPS = ("contains", "icontains", "starts_with", "ends_with", "not_contains",
+           "not_icontains", "not_starts_with", "not_ends_with")
+NULL_OPS = ("is_null", "is_not_null")
 AGGS = {"count_star": 0, "count": 1, "sum": 2, "min": 3, "max": 4}
 
 _lib = None

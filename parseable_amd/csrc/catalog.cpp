@@ -106,6 +106,8 @@ Bound ts_window(const gpuq_pred* preds, int32_t n) {
 // value in [min,max] match `op value`? can_be_pruned = !satisfy.
 bool stats_can_match(const JValue& stats, const gpuq_pred& p, int64_t lit_i,
                      double lit_f, const char* lit_s, int op) {
+  // LIKE family / IS [NOT] NULL: no min/max reasoning, never prune
+  if (op == GPUQ_CONTAINS || op >= GPUQ_ICONTAINS) return true;
   // externally tagged serde enum: {"Int": {...}} | {"Float"} | {"String"} | {"Bool"}
   if (stats.has("Int")) {
     if (p.lit_kind != GPUQ_LIT_I64) return true;  // type mismatch: cannot prune
@@ -151,9 +153,9 @@ bool stats_can_match(const JValue& stats, const gpuq_pred& p, int64_t lit_i,
 }
 
 // ManifestExt::can_be_pruned port (stream_schema_provider.rs:1049-1078):
-// a file is pruned when some predicate provably matches no row. NE and
-// CONTAINS never prune (the reference behaves the same); BETWEEN
-// decomposes into its two bounds.
+// a file is pruned when some predicate provably matches no row. NE, the
+// LIKE family (CONTAINS .. NOT_ENDS_WITH) and IS [NOT] NULL never prune
+// (the reference behaves the same); BETWEEN decomposes into its two bounds.
 bool file_pruned(const JValue& fe, const gpuq_pred* preds, int32_t n) {
   const JValue* cols = fe.get("columns");
   if (!cols || cols->kind != JValue::ARR) return false;
@@ -167,6 +169,10 @@ bool file_pruned(const JValue& fe, const gpuq_pred* preds, int32_t n) {
   for (int32_t i = 0; i < n; i++) {
     const auto& p = preds[i];
     if (p.op == GPUQ_NE || p.op == GPUQ_CONTAINS || !p.column) continue;
+    // the rest of the LIKE family and IS [NOT] NULL never prune on min/max
+    // either (manifest stats carry no null counts; a null op's literal
+    // fields are undefined and must not reach stats_can_match)
+    if (p.op >= GPUQ_ICONTAINS && p.op <= GPUQ_IS_NOT_NULL) continue;
     const JValue* st = find_stats(p.column);
     if (!st || st->kind != JValue::OBJ) continue;
     if (p.op == GPUQ_BETWEEN) {
@@ -200,7 +206,8 @@ CatalogPlanInput catalog_plan(const std::string& stream_dir,
   // pred for file-level ts pruning, so keep the full list for file_pruned)
   bool has_value_preds = false;
   for (int32_t i = 0; i < n_preds; i++)
-    if (!preds[i].column || strcmp(preds[i].column, "p_timestamp") != 0)
+    if (!preds[i].column || strcmp(preds[i].column, "p_timestamp") != 0 ||
+        preds[i].op == GPUQ_IS_NULL || preds[i].op == GPUQ_IS_NOT_NULL)
       has_value_preds = true;
 
   std::vector<JPtr> kept_files;

@@ -72,6 +72,12 @@ struct DevCWin {
 // comparison kernel ops (matches gpuq_op order where applicable)
 enum CmpMode { CMP_EQ = 0, CMP_NE, CMP_LT, CMP_LE, CMP_GT, CMP_GE, CMP_RANGE };
 
+// LIKE-family match mode: a StrKind with STRF_* flags or'ed on. FOLD lowers
+// ASCII 'A'-'Z' in the haystack (the needle arrives lower-cased from the
+// host); NEG flips the result for non-null rows only.
+enum StrKind { STR_CONTAINS = 0, STR_PREFIX = 1, STR_SUFFIX = 2 };
+enum { STRF_KIND = 3, STRF_FOLD = 4, STRF_NEG = 8 };
+
 enum { AGGK_COUNT_STAR = 0, AGGK_COUNT, AGGK_SUM_I64, AGGK_SUM_F64,
        AGGK_MIN_I64, AGGK_MAX_I64, AGGK_MIN_F64, AGGK_MAX_F64,
        AGGK_MIN_RANK, AGGK_MAX_RANK,   // utf8 min/max via dict sort-ranks

@@ -22,6 +22,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cstring>
 #include <thread>
@@ -176,7 +177,9 @@ struct ColPlan {
   // predicate routing
   std::vector<int> lut_preds;      // preds evaluated per-dict-entry (utf8)
   std::vector<int> cmp_preds;      // preds on the decoded i64 array
-  std::vector<int> contains_preds; // CONTAINS on byte_array pages
+  std::vector<int> contains_preds; // LIKE-family preds (window path on PLAIN
+                                   // byte_array pages)
+  std::vector<int> null_preds;     // IS [NOT] NULL (def levels only)
   bool need_rank = false;   // utf8 min/max: values decoded as dict sort-ranks
   bool is_bin = false;       // DATE_BIN pseudo-column (query/mod.rs:665-735)
   int bin_src = -1;          // source column index (p_timestamp)
@@ -244,7 +247,9 @@ struct RgRef {
 
 // decode-task lists per (kind,col); ids index into the partition's page array
 enum TaskKind { TK_DICT_GID, TK_DICT_VAL, TK_PLAIN_VAL, TK_DELTA_VAL,
-                TK_DICT_MASK, TK_BYTES_CONTAINS, TK_POOL_VAL, TK_N };
+                TK_DICT_MASK, TK_BYTES_CONTAINS, TK_POOL_VAL,
+                TK_IS_NULL, TK_IS_NOT_NULL,  // def levels of any encoding
+                TK_N };
 
 struct Partition {
   int device = -1;
@@ -445,13 +450,62 @@ int find_or_add_col(std::vector<ColPlan>& cols, const std::string& name) {
   return (int)cols.size() - 1;
 }
 
+// LIKE family (CONTAINS and the seven ops added after it): utf8 only, routed
+// to the LUT / window / hash paths, never pruned or elided by min/max stats
+bool op_is_like(int op) {
+  return op == GPUQ_CONTAINS || (op >= GPUQ_ICONTAINS && op <= GPUQ_NOT_ENDS_WITH);
+}
+bool op_is_null(int op) { return op == GPUQ_IS_NULL || op == GPUQ_IS_NOT_NULL; }
+// kernel match mode (dev_types.h StrKind | STRF_*) of a LIKE-family op
+int like_mode(int op) {
+  switch (op) {
+    case GPUQ_ICONTAINS: return STR_CONTAINS | STRF_FOLD;
+    case GPUQ_STARTS_WITH: return STR_PREFIX;
+    case GPUQ_ENDS_WITH: return STR_SUFFIX;
+    case GPUQ_NOT_CONTAINS: return STR_CONTAINS | STRF_NEG;
+    case GPUQ_NOT_ICONTAINS: return STR_CONTAINS | STRF_FOLD | STRF_NEG;
+    case GPUQ_NOT_STARTS_WITH: return STR_PREFIX | STRF_NEG;
+    case GPUQ_NOT_ENDS_WITH: return STR_SUFFIX | STRF_NEG;
+    default: return STR_CONTAINS;
+  }
+}
+const char* op_name(int op) {
+  static const char* names[] = {
+      "eq", "ne", "lt", "le", "gt", "ge", "between", "contains", "icontains",
+      "starts_with", "ends_with", "not_contains", "not_icontains",
+      "not_starts_with", "not_ends_with", "is_null", "is_not_null"};
+  return (op >= 0 && op <= GPUQ_IS_NOT_NULL) ? names[op] : "?";
+}
+
+// IS [NOT] NULL against one chunk's footer: null_count == 0 (or a required
+// column) proves IS NOT NULL and makes IS NULL unsatisfiable; null_count ==
+// num_values is the mirror image; anything else needs the per-row task.
+enum NullState { NULLP_EVAL = 0, NULLP_PROVEN, NULLP_UNSAT };
+NullState null_pred_state(int op, const ColumnChunkMeta& cm, bool optional) {
+  const bool none_null = !optional || cm.null_count == 0;
+  const bool all_null = optional && cm.null_count >= 0 &&
+                        cm.null_count == cm.num_values && cm.num_values > 0;
+  if (op == GPUQ_IS_NOT_NULL)
+    return none_null ? NULLP_PROVEN : all_null ? NULLP_UNSAT : NULLP_EVAL;
+  return none_null ? NULLP_UNSAT : all_null ? NULLP_PROVEN : NULLP_EVAL;
+}
+
 // row-group-level min/max pruning for i64 comparisons — the row-group analog
 // of ManifestExt::can_be_pruned + satisfy_constraints
 // (stream_schema_provider.rs:1049-1137): prune when the predicate can match
-// NO value in [min,max].
+// NO value in [min,max]. The LIKE family never prunes; IS [NOT] NULL prunes
+// on the footer null_count alone (its literal fields are undefined).
 bool rg_pruned_by_stats(const gpuq_plan& plan, const FileMeta& fm,
                         const RowGroupMeta& rg) {
   for (const auto& pp : plan.preds) {
+    if (op_is_like(pp.p.op)) continue;
+    if (op_is_null(pp.p.op)) {
+      int ci = fm.col_index(pp.col);
+      if (ci >= 0 && null_pred_state(pp.p.op, rg.chunks[ci],
+                                     fm.columns[ci].optional) == NULLP_UNSAT)
+        return true;
+      continue;
+    }
     if (pp.p.lit_kind != GPUQ_LIT_I64) continue;
     int ci = fm.col_index(pp.col);
     if (ci < 0) continue;
@@ -485,7 +539,12 @@ bool rg_pruned_by_stats(const gpuq_plan& plan, const FileMeta& fm,
 // their memset-1 selection mask and, when the column is predicate-only,
 // are never decoded at all. Requires null_count == 0: a NULL row must not
 // satisfy any predicate.
-bool pred_all_true(const gpuq_pred& p, const ColumnChunkMeta& cm) {
+bool pred_all_true(const gpuq_pred& p, const ColumnChunkMeta& cm,
+                   bool optional) {
+  // explicit, not by accident of default: a null op's zero-initialised
+  // lit_kind reads as GPUQ_LIT_I64 with a meaningless literal
+  if (op_is_like(p.op)) return false;
+  if (op_is_null(p.op)) return null_pred_state(p.op, cm, optional) == NULLP_PROVEN;
   if (p.lit_kind != GPUQ_LIT_I64 || !cm.has_i64_stats) return false;
   if (cm.null_count != 0) return false;
   int64_t mn = cm.stat_min, mx = cm.stat_max;
@@ -510,6 +569,34 @@ bool eval_str_pred(const gpuq_pred& p, const std::string& lit,
     if (lit.empty()) return true;
     if (len < lit.size()) return false;
     return memmem(s, len, lit.data(), lit.size()) != nullptr;
+  }
+  if (op_is_like(p.op)) {
+    // same semantics as k_like_win / k_affix_win / k_cmp_str, so the dict
+    // pages and the PLAIN pages of one chunk agree; `lit` is already
+    // lower-cased for the folding ops. The LUT covers dict entries only —
+    // NULL rows are zeroed by the expand mode, negated ops included.
+    const int m = like_mode(p.op);
+    bool ok = false;
+    if (lit.empty()) ok = true;
+    else if (len >= lit.size()) {
+      const size_t nl = lit.size();
+      auto fc = [&](uint8_t c) -> uint8_t {
+        return ((m & STRF_FOLD) && c >= 'A' && c <= 'Z') ? (uint8_t)(c | 0x20) : c;
+      };
+      auto at = [&](const uint8_t* b) {
+        for (size_t k = 0; k < nl; k++)
+          if (fc(b[k]) != (uint8_t)lit[k]) return false;
+        return true;
+      };
+      switch (m & STRF_KIND) {
+        case STR_PREFIX: ok = at(s); break;
+        case STR_SUFFIX: ok = at(s + len - nl); break;
+        default:
+          for (size_t j = 0; j + nl <= len && !ok; j++) ok = at(s + j);
+          break;
+      }
+    }
+    return (m & STRF_NEG) ? !ok : ok;
   }
   int c = memcmp(s, lit.data(), std::min((size_t)len, lit.size()));
   if (c == 0) c = (len < lit.size()) ? -1 : (len > lit.size() ? 1 : 0);
@@ -732,7 +819,10 @@ extern "C" gpuq_plan* gpuq_plan_build(
     PredPlan pp;
     pp.p = preds[i];
     pp.col = preds[i].column;
-    if (preds[i].str) pp.str_lit = preds[i].str;
+    if (pp.p.op < GPUQ_EQ || pp.p.op > GPUQ_IS_NOT_NULL)
+      throw std::runtime_error("unknown predicate op on " + pp.col);
+    // a null op carries no literal: its lit_kind/str/i64/f64 are not read
+    if (!op_is_null(pp.p.op) && preds[i].str) pp.str_lit = preds[i].str;
     plan->preds.push_back(std::move(pp));
   }
   for (int32_t i = 0; i < n_group_by; i++) {
@@ -800,10 +890,33 @@ extern "C" gpuq_plan* gpuq_plan_build(
       c.phys = fm0.columns[si].phys_type;
       c.optional = fm0.columns[si].optional;
     }
+    if (op_is_null(pp.p.op)) {
+      if (c.phys != PT_BYTE_ARRAY && c.phys != PT_INT64 &&
+          c.phys != PT_INT32 && c.phys != PT_DOUBLE)
+        throw std::runtime_error("unsupported predicate column type: " + pp.col);
+      c.null_preds.push_back((int)pi);
+      continue;
+    }
+    if (op_is_like(pp.p.op) && pp.p.op != GPUQ_CONTAINS &&
+        c.phys != PT_BYTE_ARRAY)
+      throw std::runtime_error(std::string("string predicate ") +
+                               op_name(pp.p.op) + " on non-utf8 column: " +
+                               pp.col);
     if (c.phys == PT_BYTE_ARRAY) {
       if (pp.p.lit_kind != GPUQ_LIT_STR)
         throw std::runtime_error("string column needs string literal: " + pp.col);
-      if (pp.p.op == GPUQ_CONTAINS) c.contains_preds.push_back((int)pi);
+      if (op_is_like(pp.p.op) && (like_mode(pp.p.op) & STRF_FOLD)) {
+        // ASCII-only folding: lower-case the needle once here; a literal
+        // with a byte >= 0x80 would need Unicode case mapping on both sides
+        for (char& ch : pp.str_lit) {
+          if ((unsigned char)ch >= 0x80)
+            throw std::runtime_error(
+                std::string(op_name(pp.p.op)) + " literal must be ASCII "
+                "(case folding is ASCII-only): " + pp.col);
+          if (ch >= 'A' && ch <= 'Z') ch = (char)(ch | 0x20);
+        }
+      }
+      if (op_is_like(pp.p.op)) c.contains_preds.push_back((int)pi);
       c.lut_preds.push_back((int)pi);   // dict pages via LUT (incl. contains)
     } else if (c.phys == PT_INT64 || c.phys == PT_INT32) {
       if (pp.p.lit_kind != GPUQ_LIT_I64)
@@ -898,6 +1011,8 @@ extern "C" gpuq_plan* gpuq_plan_build(
 
   // --- select row groups (caller's list + footer-stats pruning) ---
   std::vector<RgRef> selected;
+  // per null predicate: row groups by NullState (plan debug line)
+  std::map<size_t, std::array<int64_t, 3>> null_dbg;
   for (int32_t i = 0; i < n_files; i++) {
     const auto& mf = *plan->files[i];
     std::vector<int32_t> rg_list;
@@ -907,7 +1022,18 @@ extern "C" gpuq_plan* gpuq_plan_build(
       for (size_t g = 0; g < mf.meta.row_groups.size(); g++) rg_list.push_back((int32_t)g);
     for (int32_t g : rg_list) {
       const auto& rg = mf.meta.row_groups[g];
-      if (rg_pruned_by_stats(*plan, mf.meta, rg)) continue;
+      if (rg_pruned_by_stats(*plan, mf.meta, rg)) {
+        // debug accounting: which null predicates dropped this row group
+        for (size_t pi = 0; pi < plan->preds.size(); pi++) {
+          const auto& pp = plan->preds[pi];
+          if (!op_is_null(pp.p.op)) continue;
+          int si = mf.meta.col_index(pp.col);
+          if (si >= 0 && null_pred_state(pp.p.op, rg.chunks[si],
+                                         mf.meta.columns[si].optional) == NULLP_UNSAT)
+            null_dbg[pi][NULLP_UNSAT]++;
+        }
+        continue;
+      }
       RgRef r;
       r.file_idx = i;
       r.rg_idx = g;
@@ -950,7 +1076,7 @@ extern "C" gpuq_plan* gpuq_plan_build(
       if (c.is_bin || c.phys != PT_BYTE_ARRAY) continue;
       bool non_like = false;
       for (int pidx : c.lut_preds)
-        non_like |= (plan->preds[pidx].p.op != GPUQ_CONTAINS);
+        non_like |= !op_is_like(plan->preds[pidx].p.op);
       if (!(c.need_gid || c.need_rank || non_like)) continue;
       for (auto& r : selected) {
         const auto& mf = *plan->files[r.file_idx];
@@ -1023,6 +1149,7 @@ extern "C" gpuq_plan* gpuq_plan_build(
       uint64_t raw_off;
       uint32_t rstart;
       bool need_val_decode;
+      bool need_is_null, need_is_not_null;  // null preds the footer left open
     };
     std::vector<Stub> stubs;
     for (auto& r : part.rgs) {
@@ -1034,8 +1161,12 @@ extern "C" gpuq_plan* gpuq_plan_build(
         const auto& pp = plan->preds[pi2];
         int si = mf.meta.col_index(pp.col);
         bool elided = false;
-        if (si >= 0) elided = pred_all_true(pp.p, rg.chunks[si]);
+        if (si >= 0)
+          elided = pred_all_true(pp.p, rg.chunks[si],
+                                 mf.meta.columns[si].optional);
         pred_eval[pi2] = !elided;
+        if (op_is_null(pp.p.op))
+          null_dbg[pi2][elided ? NULLP_PROVEN : NULLP_EVAL]++;
         if (!elided) {
           auto& rv = part.pred_ranges[(int)pi2];
           int64_t lo2 = r.row_start, n2 = r.rows;
@@ -1053,8 +1184,13 @@ extern "C" gpuq_plan* gpuq_plan_build(
         const auto& cm = rg.chunks[si];
         bool needs_val = c.val_always;
         for (int pidx : c.cmp_preds) needs_val |= pred_eval[pidx];
+        bool is_null = false, is_not_null = false;
+        for (int pidx : c.null_preds) {
+          if (!pred_eval[pidx]) continue;
+          (plan->preds[pidx].p.op == GPUQ_IS_NULL ? is_null : is_not_null) = true;
+        }
         stubs.push_back({r.file_idx, r.rg_idx, (int)ci, &cm, part.raw_bytes,
-                         r.row_start, needs_val});
+                         r.row_start, needs_val, is_null, is_not_null});
         part.raw_bytes += cm.total_compressed_size;
         part.bytes_scanned += cm.total_compressed_size;
       }
@@ -1489,7 +1625,8 @@ extern "C" gpuq_plan* gpuq_plan_build(
             dp.aux_lut = lut_base;
             cb.tasks[{TK_DICT_MASK, t.col_idx}].push_back(this_pid);
           } else if (pi.encoding == ENC_PLAIN) {
-            // PLAIN fallback page of a string column: only CONTAINS supported
+            // PLAIN fallback page of a string column: the LIKE family only
+            // (an EQ..GE predicate would have put the column in hash mode)
             if ((int)c.contains_preds.size() != (int)c.lut_preds.size())
               throw std::runtime_error("non-LIKE predicate on PLAIN utf8 pages: next row");
             cb.tasks[{TK_BYTES_CONTAINS, t.col_idx}].push_back(this_pid);
@@ -1499,6 +1636,12 @@ extern "C" gpuq_plan* gpuq_plan_build(
                                  t.cm->codec, t.col_idx});
           } else throw std::runtime_error("unsupported encoding for string predicate");
         }
+        // IS [NOT] NULL reads the def levels alone: every data page of the
+        // chunk, whatever its value encoding
+        if (stubs[ti].need_is_null)
+          cb.tasks[{TK_IS_NULL, t.col_idx}].push_back(this_pid);
+        if (stubs[ti].need_is_not_null)
+          cb.tasks[{TK_IS_NOT_NULL, t.col_idx}].push_back(this_pid);
         cb.pages.push_back(dp);
       }
       if (row_in_rg != (uint32_t)mf.meta.row_groups[t.rg_idx].num_rows)
@@ -1841,6 +1984,7 @@ extern "C" gpuq_plan* gpuq_plan_build(
     bool ok = c.phys == PT_INT64 && !c.is_bin && !c.hash_mode &&
               !c.numeric_key && !c.need_gid && !c.need_rank &&
               c.cmp_preds.empty() && c.lut_preds.empty() &&
+              c.null_preds.empty() &&
               plan->group_cols[0] != vc;
     for (auto& o : plan->cols) ok &= !(o.is_bin && o.bin_src == vc);
     const bool late = kc.hash_mode || kc.numeric_key;
@@ -1886,6 +2030,37 @@ extern "C" gpuq_plan* gpuq_plan_build(
               pt.piece_pool.size(), pt.raw_bytes / 1e9, pt.dec_bytes / 1e9,
               pt.cwins.size());
     }
+    // one line per string / null predicate: the path that evaluates it
+    for (size_t pi = 0; pi < plan->preds.size(); pi++) {
+      const auto& pp = plan->preds[pi];
+      std::string path;
+      if (op_is_like(pp.p.op)) {
+        int ci = find_or_add_col(plan->cols, pp.col);
+        if (plan->cols[ci].hash_mode) {
+          path = "hash";
+        } else {
+          bool lut = false, win = false;
+          for (auto& part : plan->parts) {
+            lut |= part.tasks.count({TK_DICT_MASK, ci}) != 0;
+            win |= part.tasks.count({TK_BYTES_CONTAINS, ci}) != 0;
+          }
+          path = lut && win ? "lut+window" : win ? "window" : lut ? "lut" : "pruned";
+        }
+        fprintf(stderr, "[gpuq plan] pred %zu col=%s op=%s path=%s\n", pi,
+                pp.col.c_str(), op_name(pp.p.op), path.c_str());
+      } else if (op_is_null(pp.p.op)) {
+        const auto& n = null_dbg[pi];
+        static const char* nm[] = {"nulltask", "proven", "pruned"};
+        for (int k = 0; k < 3; k++)
+          if (n[k]) path += (path.empty() ? "" : "+") + std::string(nm[k]);
+        if (path.empty()) path = "pruned";
+        fprintf(stderr,
+                "[gpuq plan] pred %zu col=%s op=%s path=%s rowgroups: "
+                "nulltask=%lld proven=%lld pruned=%lld\n",
+                pi, pp.col.c_str(), op_name(pp.p.op), path.c_str(),
+                (long long)n[0], (long long)n[1], (long long)n[2]);
+      }
+    }
   }
   return plan.release();
 } catch (const std::exception& e) {
@@ -1923,10 +2098,20 @@ extern "C" gpuq_plan* gpuq_plan_build_from_stream(
     files[i].row_groups = nullptr;
     files[i].n_row_groups = -1;
   }
-  return gpuq_plan_build(ctx, files.data(), (int32_t)files.size(),
-                         projection, n_projection,
-                         preds, n_preds, group_by, n_group_by, aggs, n_aggs,
-                         limit);
+  gpuq_plan* plan = gpuq_plan_build(ctx, files.data(), (int32_t)files.size(),
+                                    projection, n_projection,
+                                    preds, n_preds, group_by, n_group_by,
+                                    aggs, n_aggs, limit);
+  // footer null counts can drop every row group of every kept file (IS NULL
+  // on a required column): the empty relation, like an all-pruned file list
+  bool null_pred = false;
+  for (int32_t i = 0; i < n_preds; i++) null_pred |= op_is_null(preds[i].op);
+  if (plan && null_pred && plan->m_rows_scanned == 0) {
+    gpuq_plan_destroy(plan);
+    if (fast_count) *fast_count = -2;
+    return nullptr;
+  }
+  return plan;
 } catch (const std::exception& e) {
   if (ctx) ctx->set_error(e.what());
   return nullptr;
@@ -2769,16 +2954,37 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
                           part.d_tmpvalid, part.d_mask, part.d_rowof,
                           part.d_rank, part.d_present, part.d_err);
         auto rng = part.cwin_ranges.at(col);
-        // one launch per CONTAINS pred, each with its own needle (mask &=)
+        // one launch per LIKE-family pred, each with its own needle (mask
+        // &=); plain CONTAINS keeps its own kernel
         for (int pidx : plan->cols[col].contains_preds) {
           const std::string& lit = plan->preds[pidx].str_lit;
-          launch_contains_win(st, part.d_dec, part.d_cwins + rng.first,
-                              (int)rng.second, part.d_pages, part.d_cstarts,
-                              part.d_needle + part.needle_off[pidx],
-                              (int)lit.size(), part.d_rowof, part.d_mask);
+          if (plan->preds[pidx].p.op == GPUQ_CONTAINS)
+            launch_contains_win(st, part.d_dec, part.d_cwins + rng.first,
+                                (int)rng.second, part.d_pages, part.d_cstarts,
+                                part.d_needle + part.needle_off[pidx],
+                                (int)lit.size(), part.d_rowof, part.d_mask);
+          else
+            launch_like_win(st, part.d_dec, part.d_cwins + rng.first,
+                            (int)rng.second, part.d_pages, part.d_cstarts,
+                            part.d_needle + part.needle_off[pidx],
+                            (int)lit.size(), like_mode(plan->preds[pidx].p.op),
+                            part.d_rowof, part.d_mask);
         }
         break;
       }
+      case TK_IS_NOT_NULL:
+        // the null_mask output clears NULL rows; all-valid pages return early
+        launch_def_levels(st, part.d_dec, part.d_pages, ids, n,
+                          part.d_tmpvalid, part.d_mask, nullptr, nullptr,
+                          part.d_present, part.d_err);
+        break;
+      case TK_IS_NULL:
+        launch_def_levels(st, part.d_dec, part.d_pages, ids, n,
+                          part.d_tmpvalid, nullptr, nullptr, nullptr,
+                          part.d_present, part.d_err);
+        launch_null_clear_valid(st, part.d_dec, part.d_pages, ids, n,
+                                part.d_tmpvalid, part.d_mask);
+        break;
     }
   };
   for (auto& kv : part.tasks) {
@@ -2836,7 +3042,8 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
           case GPUQ_LT: op = CMP_LT; break;
           case GPUQ_LE: op = CMP_LE; break;
           case GPUQ_GT: op = CMP_GT; break;
-          default: op = CMP_GE; break;
+          case GPUQ_GE: op = CMP_GE; break;
+          default: op = -1 - like_mode(pp.p.op); break;  // LIKE family
         }
         auto itv = part.d_valid.find((int)ci);
         launch_cmp_str(st, part.d_dec, part.d_val[(int)ci],

@@ -1301,9 +1301,24 @@ __global__ void k_numhash_lookup(const int64_t* __restrict__ vals,
   }
 }
 
+// ASCII case fold: 'A'-'Z' -> 'a'-'z', every other byte (>= 0x80 included)
+// unchanged. fold4 is the SWAR form over four bytes: per byte, bit 7 of
+// (t + 0x3f) is set for t >= 'A' and bit 7 of (t + 0x25) for t > 'Z' (t is
+// the low 7 bits, so neither add carries into the next byte); ~w drops
+// bytes >= 0x80; the surviving bit 7 moves down to 0x20.
+__device__ __forceinline__ uint8_t fold1(uint8_t c) {
+  return (uint8_t)(c - 'A') < 26u ? (uint8_t)(c | 0x20) : c;
+}
+__device__ __forceinline__ uint32_t fold4(uint32_t w) {
+  uint32_t t = w & 0x7f7f7f7fu;
+  uint32_t up = (t + 0x3f3f3f3fu) & ~(t + 0x25252525u) & ~w & 0x80808080u;
+  return w | (up >> 2);
+}
+
 // string predicates over row strrefs (mixed dict/PLAIN chunks where the
-// per-dict-entry LUT cannot cover the PLAIN pages). op: CmpMode, or -1 for
-// CONTAINS (byte substring).
+// per-dict-entry LUT cannot cover the PLAIN pages). op: CmpMode, -1 for
+// CONTAINS (byte substring), or -1 - (StrKind | STRF_*) for the other
+// LIKE-family modes (fold, prefix, suffix, negation).
 __global__ void k_cmp_str(const uint8_t* __restrict__ dec,
                           const int64_t* __restrict__ refs,
                           const uint8_t* __restrict__ valid,
@@ -1317,7 +1332,29 @@ __global__ void k_cmp_str(const uint8_t* __restrict__ dec,
     uint32_t len = ref_len(dec, ref);
     const uint8_t* s = dec + ref + 4;
     bool ok;
-    if (op < 0) {  // CONTAINS
+    if (op < -1) {  // LIKE family beyond plain CONTAINS: mode = -1 - op
+      const int m = -1 - op;
+      const int kind = m & STRF_KIND;
+      const bool fold = (m & STRF_FOLD) != 0;
+      ok = false;
+      if (lit_len == 0) ok = true;
+      else if (len >= lit_len) {
+        if (kind == STR_CONTAINS) {
+          for (uint32_t j = 0; j + lit_len <= len && !ok; j++) {
+            uint32_t k = 0;
+            while (k < lit_len &&
+                   (fold ? fold1(s[j + k]) : s[j + k]) == lit[k]) k++;
+            ok = (k == lit_len);
+          }
+        } else {  // head or tail; len >= lit_len guards the tail address
+          const uint8_t* b = s + (kind == STR_SUFFIX ? len - lit_len : 0u);
+          uint32_t k = 0;
+          while (k < lit_len && (fold ? fold1(b[k]) : b[k]) == lit[k]) k++;
+          ok = (k == lit_len);
+        }
+      }
+      if (m & STRF_NEG) ok = !ok;  // valid rows only: nulls were cleared above
+    } else if (op < 0) {  // CONTAINS
       ok = false;
       if (lit_len == 0) ok = true;
       else if (len >= lit_len) {
@@ -1680,6 +1717,243 @@ k_contains_win(const uint8_t* __restrict__ dec,
     uint32_t di = W.dense0 + i;
     mask[direct ? row0 + di : rowof[row0 + di]] &= hit;
   }
+}
+
+// k_contains_win's sibling for the substring modes it does not cover:
+// ASCII-folded (ICONTAINS) and/or negated (NOT_CONTAINS, NOT_ICONTAINS).
+// Same design — stage, register presweep into the candidate queue, verify
+// into the match-start bitmap, per-value range checks — kept as a separate
+// kernel so the plain CONTAINS instantiation stays exactly as measured.
+// FOLD: the LDS image stays EXACT (it also holds each value's u32 length
+// prefix, and a length byte in 'A'..'Z' — lengths 65-90 — must read back
+// unfolded); haystack bytes fold at the presweep (registers) and at the
+// verify compare. A presweep candidate that starts on a length byte is
+// harmless: the per-value range [o+4, o+4+vl-nlen] never includes it.
+// neg flips the hit of the value's own row; null rows were zeroed by the
+// k_def_levels launch and are never visited here.
+template <bool FOLD>
+__global__ void __launch_bounds__(CTHREADS)
+k_like_win(const uint8_t* __restrict__ dec,
+           const DevCWin* __restrict__ wins, int n,
+           const DevPage* __restrict__ pages,
+           const uint16_t* __restrict__ starts_pool,
+           const uint8_t* __restrict__ needle, int nlen, int neg,
+           const uint32_t* __restrict__ rowof, uint8_t* __restrict__ mask) {
+  __shared__ uint8_t win[CWIN];
+  __shared__ uint32_t bm[CWIN / 32];
+  __shared__ uint16_t q[CQMAX];
+  __shared__ uint32_t qn;
+  __shared__ int shit;
+  if (blockIdx.x >= (unsigned)n) return;
+  const DevCWin W = wins[blockIdx.x];
+  const DevPage pg = pages[W.page_id];
+  const uint32_t row0 = pg.row_start;
+  bool direct = true;
+  if (pg.optional) {
+    const uint8_t* ds; uint32_t dl; bool av;
+    def_levels(pg, dec + pg.dst_off, &ds, &dl, &av);
+    direct = av;
+  }
+  const uint8_t* src = dec + W.src;
+  auto hb = [](uint8_t c) -> uint8_t { return FOLD ? fold1(c) : c; };
+  if (W.nbytes > CWIN) {  // single oversized value: strided global scan
+    uint32_t vl;
+    __builtin_memcpy(&vl, src, 4);
+    if (threadIdx.x == 0) shit = (nlen == 0);
+    __syncthreads();
+    if (nlen && vl >= (uint32_t)nlen) {
+      for (uint32_t j = threadIdx.x; j + (uint32_t)nlen <= vl && !shit;
+           j += CTHREADS) {
+        int k = 0;
+        while (k < nlen && hb(src[4 + j + k]) == needle[k]) k++;
+        if (k == nlen) shit = 1;
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t di = W.dense0;
+      mask[direct ? row0 + di : rowof[row0 + di]] &=
+          (uint8_t)((shit != 0) ^ (neg != 0));
+    }
+    return;
+  }
+  if (threadIdx.x == 0) qn = 0;
+  __syncthreads();
+  {
+    uint32_t v[CWIN / (CTHREADS * 4)];
+#pragma unroll
+    for (int k = 0; k < CWIN / (CTHREADS * 4); k++)
+      __builtin_memcpy(&v[k], src + threadIdx.x * 4u + (uint32_t)k * (CTHREADS * 4u), 4);
+#pragma unroll
+    for (int k = 0; k < CWIN / (CTHREADS * 4); k++)
+      *(uint32_t*)&win[threadIdx.x * 4u + (uint32_t)k * (CTHREADS * 4u)] = v[k];
+    if (nlen) {
+      const uint32_t pat = 0x01010101u * needle[0];
+#pragma unroll
+      for (int k = 0; k < CWIN / (CTHREADS * 4); k++) {
+        uint32_t p = threadIdx.x * 4u + (uint32_t)k * (CTHREADS * 4u);
+        if (p >= W.nbytes) continue;
+        uint32_t x = (FOLD ? fold4(v[k]) : v[k]) ^ pat;
+        uint32_t cand = (x - 0x01010101u) & ~x & 0x80808080u;
+        while (cand) {
+          int b = (__builtin_ctz(cand)) >> 3;
+          cand &= cand - 1;
+          uint32_t qi = atomicAdd(&qn, 1u);
+          if (qi < CQMAX) q[qi] = (uint16_t)(p + b);
+        }
+      }
+    }
+  }
+  for (uint32_t i = threadIdx.x; i < CWIN / 32; i += CTHREADS) bm[i] = 0;
+  __syncthreads();
+  if (nlen) {
+    if (qn <= CQMAX) {
+      for (uint32_t i = threadIdx.x; i < qn; i += CTHREADS) {
+        uint32_t pos = q[i];
+        if (pos + nlen <= CWIN) {
+          int k = 0;
+          while (k < nlen && hb(win[pos + k]) == needle[k]) k++;
+          if (k == nlen) atomicOr(&bm[pos >> 5], 1u << (pos & 31));
+        }
+      }
+    } else {  // queue overflow: full sweep from LDS
+      for (uint32_t p = threadIdx.x * 4u; p < W.nbytes; p += CTHREADS * 4u) {
+        uint32_t w = *(const uint32_t*)&win[p];
+        uint32_t x = (FOLD ? fold4(w) : w) ^ pat_full(needle[0]);
+        uint32_t cand = (x - 0x01010101u) & ~x & 0x80808080u;
+        while (cand) {
+          int b = (__builtin_ctz(cand)) >> 3;
+          cand &= cand - 1;
+          uint32_t pos = p + b;
+          if (pos + nlen <= CWIN) {
+            int k = 0;
+            while (k < nlen && hb(win[pos + k]) == needle[k]) k++;
+            if (k == nlen) atomicOr(&bm[pos >> 5], 1u << (pos & 31));
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const uint32_t* win32 = (const uint32_t*)win;
+  for (uint32_t i = threadIdx.x; i < W.n_values; i += CTHREADS) {
+    uint32_t o = starts_pool[W.starts + i];
+    uint32_t sh = (o & 3) * 8;
+    uint32_t vl = win32[o >> 2] >> sh;
+    if (sh) vl |= win32[(o >> 2) + 1] << (32 - sh);
+    uint8_t hit = 0;
+    if (nlen == 0) {
+      hit = 1;
+    } else if (vl >= (uint32_t)nlen) {
+      uint32_t lo = o + 4, hi = o + 4 + vl - nlen;  // inclusive starts
+      uint32_t w0 = lo >> 5, w1 = hi >> 5;
+      if (w0 == w1) {
+        uint32_t m = (hi - lo == 31) ? ~0u
+                                     : (((1u << (hi - lo + 1)) - 1) << (lo & 31));
+        hit = (bm[w0] & m) != 0;
+      } else {
+        uint32_t m0 = ~0u << (lo & 31);
+        uint32_t m1 = ((hi & 31) == 31) ? ~0u : ((1u << ((hi & 31) + 1)) - 1);
+        hit = ((bm[w0] & m0) != 0) | ((bm[w1] & m1) != 0);
+        for (uint32_t w = w0 + 1; w < w1 && !hit; w++) hit |= (bm[w] != 0);
+      }
+    }
+    uint32_t di = W.dense0 + i;
+    mask[direct ? row0 + di : rowof[row0 + di]] &= (uint8_t)(hit ^ (neg != 0));
+  }
+}
+
+// prefix / suffix LIKE over the same windows: no candidate queue and no
+// bitmap — after staging, each thread compares nlen bytes at the head
+// (o+4) or the tail (o+4+vl-nlen) of its values. vl >= nlen is checked
+// BEFORE the tail address is formed, so a short value never reads back
+// into its neighbour.
+template <bool SUFFIX>
+__global__ void __launch_bounds__(CTHREADS)
+k_affix_win(const uint8_t* __restrict__ dec,
+            const DevCWin* __restrict__ wins, int n,
+            const DevPage* __restrict__ pages,
+            const uint16_t* __restrict__ starts_pool,
+            const uint8_t* __restrict__ needle, int nlen, int neg,
+            const uint32_t* __restrict__ rowof, uint8_t* __restrict__ mask) {
+  __shared__ uint8_t win[CWIN];
+  __shared__ int smiss;
+  if (blockIdx.x >= (unsigned)n) return;
+  const DevCWin W = wins[blockIdx.x];
+  const DevPage pg = pages[W.page_id];
+  const uint32_t row0 = pg.row_start;
+  bool direct = true;
+  if (pg.optional) {
+    const uint8_t* ds; uint32_t dl; bool av;
+    def_levels(pg, dec + pg.dst_off, &ds, &dl, &av);
+    direct = av;
+  }
+  const uint8_t* src = dec + W.src;
+  if (W.nbytes > CWIN) {  // single oversized value: compare in global memory
+    uint32_t vl;
+    __builtin_memcpy(&vl, src, 4);
+    if (threadIdx.x == 0) smiss = (vl < (uint32_t)nlen);
+    __syncthreads();
+    if (vl >= (uint32_t)nlen) {
+      const uint8_t* s = src + 4 + (SUFFIX ? vl - (uint32_t)nlen : 0u);
+      for (int k = threadIdx.x; k < nlen; k += CTHREADS)
+        if (s[k] != needle[k]) smiss = 1;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t di = W.dense0;
+      mask[direct ? row0 + di : rowof[row0 + di]] &=
+          (uint8_t)((smiss == 0) ^ (neg != 0));
+    }
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < CWIN / (CTHREADS * 4); k++) {
+    uint32_t p = threadIdx.x * 4u + (uint32_t)k * (CTHREADS * 4u);
+    uint32_t v;
+    __builtin_memcpy(&v, src + p, 4);
+    *(uint32_t*)&win[p] = v;
+  }
+  __syncthreads();
+  const uint32_t* win32 = (const uint32_t*)win;
+  for (uint32_t i = threadIdx.x; i < W.n_values; i += CTHREADS) {
+    uint32_t o = starts_pool[W.starts + i];
+    uint32_t sh = (o & 3) * 8;
+    uint32_t vl = win32[o >> 2] >> sh;
+    if (sh) vl |= win32[(o >> 2) + 1] << (32 - sh);
+    uint8_t hit = 0;
+    if (vl >= (uint32_t)nlen) {
+      uint32_t b = o + 4 + (SUFFIX ? vl - (uint32_t)nlen : 0u);
+      int k = 0;
+      while (k < nlen && win[b + k] == needle[k]) k++;
+      hit = (k == nlen);
+    }
+    uint32_t di = W.dense0 + i;
+    mask[direct ? row0 + di : rowof[row0 + di]] &= (uint8_t)(hit ^ (neg != 0));
+  }
+}
+
+// IS NULL over the data pages of one column (any encoding): clears the
+// VALID rows of those pages from the mask. Runs after k_def_levels, which
+// wrote valid[] for null-bearing pages only — an all-valid page (required
+// column, or one RLE run of 1s) left valid[] untouched there, so the same
+// probe decides here and clears the whole page.
+__global__ void __launch_bounds__(CTHREADS)
+k_null_clear_valid(const uint8_t* __restrict__ dec,
+                   const DevPage* __restrict__ pages,
+                   const int32_t* __restrict__ ids, int n,
+                   const uint8_t* __restrict__ valid,
+                   uint8_t* __restrict__ mask) {
+  if (blockIdx.x >= (unsigned)n) return;
+  const DevPage pg = pages[ids[blockIdx.x]];
+  bool av = true;
+  if (pg.optional) {
+    const uint8_t* ds; uint32_t dl;
+    def_levels(pg, dec + pg.dst_off, &ds, &dl, &av);
+  }
+  const uint32_t row0 = pg.row_start;
+  for (uint32_t r = threadIdx.x; r < pg.num_values; r += CTHREADS)
+    if (av || valid[row0 + r]) mask[row0 + r] = 0;
 }
 
 __global__ void k_cmp_i64(const int64_t* __restrict__ col,
@@ -2382,6 +2656,30 @@ void launch_contains_win(hipStream_t st, const uint8_t* dec,
                          const uint16_t* starts_pool, const uint8_t* needle,
                          int nlen, const uint32_t* rowof, uint8_t* mask) {
   if (n) hipLaunchKernelGGL(k_contains_win, dim3(n), dim3(CTHREADS), 0, st, dec, wins, n, pages, starts_pool, needle, nlen, rowof, mask);
+}
+void launch_like_win(hipStream_t st, const uint8_t* dec, const DevCWin* wins,
+                     int n, const DevPage* pages, const uint16_t* starts_pool,
+                     const uint8_t* needle, int nlen, int mode,
+                     const uint32_t* rowof, uint8_t* mask) {
+  if (!n) return;
+  const int neg = (mode & STRF_NEG) ? 1 : 0;
+#define GPUQ_LIKE_LAUNCH(K) \
+  hipLaunchKernelGGL(K, dim3(n), dim3(CTHREADS), 0, st, dec, wins, n, pages, \
+                     starts_pool, needle, nlen, neg, rowof, mask)
+  switch (mode & STRF_KIND) {
+    case STR_PREFIX: GPUQ_LIKE_LAUNCH(k_affix_win<false>); break;
+    case STR_SUFFIX: GPUQ_LIKE_LAUNCH(k_affix_win<true>); break;
+    default:
+      if (mode & STRF_FOLD) GPUQ_LIKE_LAUNCH(k_like_win<true>);
+      else GPUQ_LIKE_LAUNCH(k_like_win<false>);
+      break;
+  }
+#undef GPUQ_LIKE_LAUNCH
+}
+void launch_null_clear_valid(hipStream_t st, const uint8_t* dec,
+                             const DevPage* pages, const int32_t* ids, int n,
+                             const uint8_t* valid, uint8_t* mask) {
+  if (n) hipLaunchKernelGGL(k_null_clear_valid, dim3(n), dim3(CTHREADS), 0, st, dec, pages, ids, n, valid, mask);
 }
 void launch_def_levels(hipStream_t st, const uint8_t* dec, const DevPage* pages,
                        const int32_t* ids, int n, uint8_t* valid,

@@ -26,7 +26,8 @@ import json
 import os
 
 from . import _lib
-from ._lib import AGGS, OPS, GpuqAgg, GpuqFile, GpuqPred, GpuqMetrics
+from ._lib import (AGGS, NULL_OPS, OPS, STR_OPS, GpuqAgg, GpuqFile, GpuqPred,
+                   GpuqMetrics)
 
 
 class GpuqError(RuntimeError):
@@ -107,7 +108,9 @@ def _file_pruned(file_entry, preds):
         elif op == "ge":
             sat = mx >= value
         else:
-            return False  # ne/contains: never pruned (reference does the same)
+            # ne, the LIKE family and is_null/is_not_null: never pruned on
+            # min/max (reference does the same)
+            return False
         return not sat
 
     for p in preds:
@@ -116,8 +119,8 @@ def _file_pruned(file_entry, preds):
         if op == "between":
             if check(col, "ge", p["lo"]) or check(col, "le" if not p.get("hi_exclusive") else "lt", p["hi"]):
                 return True
-        elif op == "contains" or op == "ne":
-            continue
+        elif op == "ne" or op in STR_OPS or op in NULL_OPS:
+            continue  # no literal to compare (null ops) / no min/max reasoning
         else:
             if check(col, op, p["lit"]):
                 return True
@@ -210,6 +213,8 @@ class EmptyScanResult:
         self.query = query
 
     def rows(self):
+        if self.query.get("select_cols"):
+            return []
         return merge_partials([], self.query)
 
 
@@ -274,6 +279,12 @@ class StagingScanner:
                             else pc.less_equal(col, p["hi"]))
             elif op == "contains":
                 m = pc.match_substring(col, p["lit"])
+            elif op in STR_OPS:
+                m = _like_mask(col, op, p["lit"])
+            elif op == "is_null":
+                m = pc.is_null(col)
+            elif op == "is_not_null":
+                m = pc.is_valid(col)
             else:
                 f = {"eq": pc.equal, "ne": pc.not_equal, "lt": pc.less,
                      "le": pc.less_equal, "gt": pc.greater,
@@ -387,6 +398,47 @@ class StagingScanner:
                 proj.append(c.to_pylist())
             out.extend([list(r) for r in zip(*proj)])
         return out
+
+
+def _like_mask(col, op, lit):
+    """LIKE-family predicate over a utf8 column on the staging leg, with the
+    GPU leg's byte semantics (include/gpuq.h): the literal is a plain byte
+    string, the i-ops fold ASCII A-Z only (bytes.lower(); pc.utf8_lower and
+    the RE2 ignore_case are Unicode-aware and would disagree), a NULL row
+    satisfies nothing — negated ops included — and an empty literal matches
+    every non-null row (no row when negated). Evaluated once per distinct
+    value."""
+    import pyarrow as pa
+
+    if not isinstance(lit, str):
+        raise GpuqError(f"string column needs string literal: {op}")
+    neg = op.startswith("not_")
+    base = op[4:] if neg else op
+    needle = lit.encode()
+    fold = base == "icontains"
+    if fold:
+        if any(b >= 0x80 for b in needle):
+            raise GpuqError(f"{op} literal must be ASCII "
+                            "(case folding is ASCII-only)")
+        needle = needle.lower()
+    if isinstance(col, pa.ChunkedArray):
+        col = col.combine_chunks()
+    if not (pa.types.is_string(col.type) or pa.types.is_large_string(col.type)):
+        raise GpuqError(f"string predicate {op} on non-utf8 column")
+    enc = col.cast(pa.binary()).dictionary_encode()
+    lut = []
+    for v in enc.dictionary.to_pylist():
+        if fold:
+            v = v.lower()
+        if base == "starts_with":
+            ok = v.startswith(needle)
+        elif base == "ends_with":
+            ok = v.endswith(needle)
+        else:
+            ok = needle in v
+        lut.append(ok != neg)
+    # take() through the indices keeps NULL rows NULL (fill_null -> False)
+    return pa.array(lut, type=pa.bool_()).take(enc.indices)
 
 
 class StagedPlan:
@@ -600,7 +652,8 @@ class StandardTableProvider:
         for fe in kept:
             p = fe["file_path"]
             paths.append(p if os.path.isabs(p) else os.path.join(root, p))
-        return GpuExecutionPlan(self.session, paths, query)
+        plan = GpuExecutionPlan(self.session, paths, query)
+        return EmptyScanResult(query) if plan.empty else plan
 
     def _scan_with_staging(self, query):
         """Staging branch (stream_schema_provider.rs:637-647): manifest
@@ -624,6 +677,8 @@ class StandardTableProvider:
             paths.append(p if os.path.isabs(p) else os.path.join(root, p))
         paths.extend(scanner.parquet_paths())  # scanned unconditionally
         gpu_plan = GpuExecutionPlan(self.session, paths, query) if paths else None
+        if gpu_plan is not None and gpu_plan.empty:
+            gpu_plan = None
         return StagedPlan(gpu_plan, scanner, query)
 
     def _scan_with_legacy(self, query, legacy_paths):
@@ -647,7 +702,8 @@ class StandardTableProvider:
             paths.append(p if os.path.isabs(p) else os.path.join(root, p))
         if not paths:
             return EmptyScanResult(query)
-        return GpuExecutionPlan(self.session, paths, query)
+        plan = GpuExecutionPlan(self.session, paths, query)
+        return EmptyScanResult(query) if plan.empty else plan
 
 
 def _build_c_projection(query: dict, keep):
@@ -686,6 +742,9 @@ def _build_c_query(query: dict, keep):
             cpreds[i].lit_kind = 0
             cpreds[i].i64[0] = p["lo"]
             cpreds[i].i64[1] = p["hi"]
+        elif p["op"] in NULL_OPS:
+            if p.get("lit") is not None:
+                raise GpuqError(f"{p['op']} takes no literal")
         else:
             lit = p["lit"]
             if isinstance(lit, str):
@@ -772,6 +831,12 @@ class GpuExecutionPlan:
         )
         if not self._plan:
             raise GpuqError(f"plan_build failed: {session._err()}")
+        # footer null counts can drop every row group (is_null on a required
+        # column): the empty relation, as the native planner reports it
+        if (any(p["op"] in NULL_OPS for p in query.get("preds", []))
+                and self.metrics()["rows_scanned"] == 0):
+            self.close()
+            self.empty = True
 
     def partition_count(self) -> int:
         return self._lib.gpuq_plan_partition_count(self._plan)
