@@ -108,6 +108,7 @@ C6_WORDS = ["request", "Served", "retry", "from", "cache", "Zone", "queue",
             "user", "path", "GET", "put", "ok", "a", "b7", "x", "é", "É",
             "日本", "café", "État", "node", "disk", "full", "slow", "r"]
 C6_BIG_LEN = 40_000
+C6_DENSE_RUN = 320    # consecutive '='-filled messages, > 3 x 16 KiB in all
 
 
 def _c6_filler(rng, nbytes):
@@ -132,7 +133,10 @@ def _c6_batch(rng, n, minute, cols):
     dict-encoded, `message` and `tag` overflow the 4 KiB dictionary limit
     into PLAIN pages; `latency` is a REQUIRED column; `sparse` is all-NULL in
     odd minutes and null-free in even ones; minute 0 carries one 40,000-byte
-    message (Error ... TIMEOUT)."""
+    message (Error ... TIMEOUT); minute 1 carries, from its middle row on,
+    320 consecutive messages of 120-189 '=' plus a short suffix (none,
+    Error, =error, TIMEOUT, x), about 51 KB of PLAIN-page bytes over 90 %
+    '='."""
     cols["latency"] = pa.array(
         rng.integers(0, 10**6, n, dtype=np.int64), type=pa.int64())
     lv_idx = rng.integers(0, len(C6_LEVELS), n).astype(np.int32)
@@ -166,6 +170,13 @@ def _c6_batch(rng, n, minute, cols):
     for j in range(7, n - 1, 97):
         msgs[j] = _c6_filler(rng, 30) + " " + C6_TOKENS[(j // 97) % len(C6_TOKENS)]
         msgs[j + 1] = ["", "ut", "or"][(j // 97) % 3]
+    # a run dense in one byte: more candidate positions for a needle that
+    # starts with '=' than a window's candidate queue holds (draws nothing
+    # from rng, so every other value is as it was)
+    if minute == 1 and n // 2 + C6_DENSE_RUN < n:
+        for j in range(C6_DENSE_RUN):
+            msgs[n // 2 + j] = "=" * (120 + j % 70) + \
+                ["", "Error", "=error", "TIMEOUT", "x"][j % 5]
     if minute == 0 and n > 2:
         big = "Error " + _c6_filler(rng, C6_BIG_LEN - 100) + " "
         big = big + "x" * (C6_BIG_LEN - len(big.encode()) - 7) + "TIMEOUT"

@@ -77,6 +77,14 @@ enum CmpMode { CMP_EQ = 0, CMP_NE, CMP_LT, CMP_LE, CMP_GT, CMP_GE, CMP_RANGE };
 // host); NEG flips the result for non-null rows only.
 enum StrKind { STR_CONTAINS = 0, STR_PREFIX = 1, STR_SUFFIX = 2 };
 enum { STRF_KIND = 3, STRF_FOLD = 4, STRF_NEG = 8 };
+// k_cmp_str takes one op: a CmpMode as is, or a LIKE-family match mode
+// tagged with a bit above both ranges. cmp_str_like_mode() undoes the tag
+// and returns -1 for a CmpMode.
+enum { CMP_STR_LIKE = 16 };
+constexpr int cmp_str_like(int mode) { return CMP_STR_LIKE | mode; }
+constexpr int cmp_str_like_mode(int op) {
+  return (op & CMP_STR_LIKE) ? (op & ~CMP_STR_LIKE) : -1;
+}
 
 enum { AGGK_COUNT_STAR = 0, AGGK_COUNT, AGGK_SUM_I64, AGGK_SUM_F64,
        AGGK_MIN_I64, AGGK_MAX_I64, AGGK_MIN_F64, AGGK_MAX_F64,

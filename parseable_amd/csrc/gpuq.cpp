@@ -565,14 +565,9 @@ bool pred_all_true(const gpuq_pred& p, const ColumnChunkMeta& cm,
 // evaluate a string predicate against one dict entry (host; LUT build)
 bool eval_str_pred(const gpuq_pred& p, const std::string& lit,
                    const uint8_t* s, uint32_t len) {
-  if (p.op == GPUQ_CONTAINS) {
-    if (lit.empty()) return true;
-    if (len < lit.size()) return false;
-    return memmem(s, len, lit.data(), lit.size()) != nullptr;
-  }
   if (op_is_like(p.op)) {
-    // same semantics as k_like_win / k_affix_win / k_cmp_str, so the dict
-    // pages and the PLAIN pages of one chunk agree; `lit` is already
+    // same semantics as k_contains_win<> / k_affix_win<> / k_cmp_str, so the
+    // dict pages and the PLAIN pages of one chunk agree; `lit` is already
     // lower-cased for the folding ops. The LUT covers dict entries only —
     // NULL rows are zeroed by the expand mode, negated ops included.
     const int m = like_mode(p.op);
@@ -592,7 +587,8 @@ bool eval_str_pred(const gpuq_pred& p, const std::string& lit,
         case STR_PREFIX: ok = at(s); break;
         case STR_SUFFIX: ok = at(s + len - nl); break;
         default:
-          for (size_t j = 0; j + nl <= len && !ok; j++) ok = at(s + j);
+          if (!(m & STRF_FOLD)) ok = memmem(s, len, lit.data(), nl) != nullptr;
+          else for (size_t j = 0; j + nl <= len && !ok; j++) ok = at(s + j);
           break;
       }
     }
@@ -2954,21 +2950,14 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
                           part.d_tmpvalid, part.d_mask, part.d_rowof,
                           part.d_rank, part.d_present, part.d_err);
         auto rng = part.cwin_ranges.at(col);
-        // one launch per LIKE-family pred, each with its own needle (mask
-        // &=); plain CONTAINS keeps its own kernel
+        // one launch per LIKE-family pred, each with its own needle (mask &=)
         for (int pidx : plan->cols[col].contains_preds) {
           const std::string& lit = plan->preds[pidx].str_lit;
-          if (plan->preds[pidx].p.op == GPUQ_CONTAINS)
-            launch_contains_win(st, part.d_dec, part.d_cwins + rng.first,
-                                (int)rng.second, part.d_pages, part.d_cstarts,
-                                part.d_needle + part.needle_off[pidx],
-                                (int)lit.size(), part.d_rowof, part.d_mask);
-          else
-            launch_like_win(st, part.d_dec, part.d_cwins + rng.first,
-                            (int)rng.second, part.d_pages, part.d_cstarts,
-                            part.d_needle + part.needle_off[pidx],
-                            (int)lit.size(), like_mode(plan->preds[pidx].p.op),
-                            part.d_rowof, part.d_mask);
+          launch_str_win(st, part.d_dec, part.d_cwins + rng.first,
+                         (int)rng.second, part.d_pages, part.d_cstarts,
+                         part.d_needle + part.needle_off[pidx],
+                         (int)lit.size(), like_mode(plan->preds[pidx].p.op),
+                         part.d_rowof, part.d_mask);
         }
         break;
       }
@@ -3036,14 +3025,13 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
         const auto& pp = plan->preds[pidx];
         int op;
         switch (pp.p.op) {
-          case GPUQ_CONTAINS: op = -1; break;
           case GPUQ_EQ: op = CMP_EQ; break;
           case GPUQ_NE: op = CMP_NE; break;
           case GPUQ_LT: op = CMP_LT; break;
           case GPUQ_LE: op = CMP_LE; break;
           case GPUQ_GT: op = CMP_GT; break;
           case GPUQ_GE: op = CMP_GE; break;
-          default: op = -1 - like_mode(pp.p.op); break;  // LIKE family
+          default: op = cmp_str_like(like_mode(pp.p.op)); break;  // LIKE family
         }
         auto itv = part.d_valid.find((int)ci);
         launch_cmp_str(st, part.d_dec, part.d_val[(int)ci],

@@ -1316,9 +1316,8 @@ __device__ __forceinline__ uint32_t fold4(uint32_t w) {
 }
 
 // string predicates over row strrefs (mixed dict/PLAIN chunks where the
-// per-dict-entry LUT cannot cover the PLAIN pages). op: CmpMode, -1 for
-// CONTAINS (byte substring), or -1 - (StrKind | STRF_*) for the other
-// LIKE-family modes (fold, prefix, suffix, negation).
+// per-dict-entry LUT cannot cover the PLAIN pages). op: a CmpMode, or
+// cmp_str_like(StrKind | STRF_*) for the LIKE family (dev_types.h).
 __global__ void k_cmp_str(const uint8_t* __restrict__ dec,
                           const int64_t* __restrict__ refs,
                           const uint8_t* __restrict__ valid,
@@ -1332,40 +1331,30 @@ __global__ void k_cmp_str(const uint8_t* __restrict__ dec,
     uint32_t len = ref_len(dec, ref);
     const uint8_t* s = dec + ref + 4;
     bool ok;
-    if (op < -1) {  // LIKE family beyond plain CONTAINS: mode = -1 - op
-      const int m = -1 - op;
+    const int m = cmp_str_like_mode(op);
+    if (m >= 0) {  // LIKE family
       const int kind = m & STRF_KIND;
       const bool fold = (m & STRF_FOLD) != 0;
+      auto hb = [&](uint8_t c) -> uint8_t { return fold ? fold1(c) : c; };
       ok = false;
       if (lit_len == 0) ok = true;
       else if (len >= lit_len) {
         if (kind == STR_CONTAINS) {
+          const uint8_t c0 = lit[0];
           for (uint32_t j = 0; j + lit_len <= len && !ok; j++) {
-            uint32_t k = 0;
-            while (k < lit_len &&
-                   (fold ? fold1(s[j + k]) : s[j + k]) == lit[k]) k++;
+            if (hb(s[j]) != c0) continue;
+            uint32_t k = 1;
+            while (k < lit_len && hb(s[j + k]) == lit[k]) k++;
             ok = (k == lit_len);
           }
         } else {  // head or tail; len >= lit_len guards the tail address
           const uint8_t* b = s + (kind == STR_SUFFIX ? len - lit_len : 0u);
           uint32_t k = 0;
-          while (k < lit_len && (fold ? fold1(b[k]) : b[k]) == lit[k]) k++;
+          while (k < lit_len && hb(b[k]) == lit[k]) k++;
           ok = (k == lit_len);
         }
       }
       if (m & STRF_NEG) ok = !ok;  // valid rows only: nulls were cleared above
-    } else if (op < 0) {  // CONTAINS
-      ok = false;
-      if (lit_len == 0) ok = true;
-      else if (len >= lit_len) {
-        uint8_t c0 = lit[0];
-        for (uint32_t j = 0; j + lit_len <= len && !ok; j++) {
-          if (s[j] != c0) continue;
-          uint32_t k = 1;
-          while (k < lit_len && s[j + k] == lit[k]) k++;
-          ok = (k == lit_len);
-        }
-      }
     } else {
       uint32_t n = len < lit_len ? len : lit_len;
       int c = 0;
@@ -1579,14 +1568,50 @@ k_delta_i64(const uint8_t* __restrict__ dec, const DevPage* __restrict__ pages,
 #define CTHREADS 256
 #define CQMAX 4096
 __device__ inline uint32_t pat_full(uint8_t c0) { return 0x01010101u * c0; }
-// window-parallel CONTAINS over PLAIN byte-array pages: one block per
-// DevCWin. The host decompressed each page ONCE at load time, walked the
-// [u32 len][bytes] chain, and emitted value-aligned <=16KB windows plus a
-// u16 start offset per value — so the kernel has NO serial spine at all:
-// stage window -> all 256 threads sweep needle candidates (zero-byte trick,
-// verified from byte 0) into a match-start bitmap -> thread-parallel
-// per-value bitmap range checks. Null rows are zeroed by the preceding
-// k_def_levels launch (null_mask).
+// pieces shared by the window kernels (k_contains_win<>, k_affix_win<>).
+// Row mapping of a window's page: true when dense value index == row index
+// (required column or all-valid page); the probe mirrors the value decoders.
+__device__ __forceinline__ bool win_direct(const DevPage& pg,
+                                           const uint8_t* dec) {
+  bool av = true;
+  if (pg.optional) {
+    const uint8_t* ds; uint32_t dl;
+    def_levels(pg, dec + pg.dst_off, &ds, &dl, &av);
+  }
+  return av;
+}
+// u32 length prefix at byte offset o of the staged window (any alignment)
+__device__ __forceinline__ uint32_t win_vlen(const uint32_t* win32, uint32_t o) {
+  uint32_t sh = (o & 3) * 8;
+  uint32_t vl = win32[o >> 2] >> sh;
+  if (sh) vl |= win32[(o >> 2) + 1] << (32 - sh);
+  return vl;
+}
+// mask &= hit for the row of the page's dense (non-null) value di
+__device__ __forceinline__ void win_mask_and(uint8_t* mask,
+                                             const uint32_t* rowof, bool direct,
+                                             uint32_t row0, uint32_t di,
+                                             uint8_t hit) {
+  mask[direct ? row0 + di : rowof[row0 + di]] &= hit;
+}
+
+// window-parallel substring match (CONTAINS, ICONTAINS and their negations)
+// over PLAIN byte-array pages: one block per DevCWin. The host decompressed
+// each page ONCE at load time, walked the [u32 len][bytes] chain, and emitted
+// value-aligned <=16KB windows plus a u16 start offset per value — so the
+// kernel has NO serial spine at all: stage window -> all 256 threads sweep
+// needle candidates (zero-byte trick, verified from byte 0) into a
+// match-start bitmap -> thread-parallel per-value bitmap range checks. Null
+// rows are zeroed by the preceding k_def_levels launch (null_mask) and are
+// never visited here.
+// FOLD: the LDS image stays EXACT (it also holds each value's u32 length
+// prefix, and a length byte in 'A'..'Z' — lengths 65-90 — must read back
+// unfolded); haystack bytes fold at the presweep (registers) and at the
+// verify compare. A presweep candidate that starts on a length byte is
+// harmless: the per-value range [o+4, o+4+vl-nlen] never includes it.
+// NEG flips the hit of the value's own row; both are compile-time, so the
+// plain <false,false> instantiation carries neither fold nor xor.
+template <bool FOLD, bool NEG>
 __global__ void __launch_bounds__(CTHREADS)
 k_contains_win(const uint8_t* __restrict__ dec,
                const DevCWin* __restrict__ wins, int n,
@@ -1603,13 +1628,19 @@ k_contains_win(const uint8_t* __restrict__ dec,
   const DevCWin W = wins[blockIdx.x];
   const DevPage pg = pages[W.page_id];
   const uint32_t row0 = pg.row_start;
-  bool direct = true;  // row mapping: probe mirrors the value decoders
-  if (pg.optional) {
-    const uint8_t* ds; uint32_t dl; bool av;
-    def_levels(pg, dec + pg.dst_off, &ds, &dl, &av);
-    direct = av;
-  }
+  const bool direct = win_direct(pg, dec);
   const uint8_t* src = dec + W.src;
+  // needle at byte `pos` of the haystack read through get()? Verifies from
+  // byte 0: the borrow trick of the candidate sweeps has false positives.
+  // Captures needle/nlen by value: by reference the compiler schedules the
+  // verify loops differently from the measured kernel.
+  auto match_at = [=](auto get, uint32_t pos) {
+    int k = 0;
+    while (k < nlen &&
+           (FOLD ? fold1(get(pos + k)) : get(pos + k)) == needle[k]) k++;
+    return k == nlen;
+  };
+  auto win_at = [&](uint32_t i) { return win[i]; };
   if (W.nbytes > CWIN) {  // single oversized value: strided global scan
     uint32_t vl;
     __builtin_memcpy(&vl, src, 4);
@@ -1617,17 +1648,13 @@ k_contains_win(const uint8_t* __restrict__ dec,
     __syncthreads();
     if (nlen && vl >= (uint32_t)nlen) {
       for (uint32_t j = threadIdx.x; j + (uint32_t)nlen <= vl && !shit;
-           j += CTHREADS) {
-        int k = 0;
-        while (k < nlen && src[4 + j + k] == needle[k]) k++;
-        if (k == nlen) shit = 1;
-      }
+           j += CTHREADS)
+        if (match_at([&](uint32_t i) { return src[4 + i]; }, j)) shit = 1;
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-      uint32_t di = W.dense0;
-      mask[direct ? row0 + di : rowof[row0 + di]] &= (uint8_t)(shit != 0);
-    }
+    if (threadIdx.x == 0)
+      win_mask_and(mask, rowof, direct, row0, W.dense0,
+                   (uint8_t)((shit != 0) ^ NEG));
     return;
   }
   if (threadIdx.x == 0) qn = 0;
@@ -1636,150 +1663,6 @@ k_contains_win(const uint8_t* __restrict__ dec,
      // presweep needle candidates while the words are STILL IN REGISTERS —
      // the verify pass then touches only queued positions instead of
      // re-reading the whole window from LDS
-    uint32_t v[CWIN / (CTHREADS * 4)];
-#pragma unroll
-    for (int k = 0; k < CWIN / (CTHREADS * 4); k++)
-      __builtin_memcpy(&v[k], src + threadIdx.x * 4u + (uint32_t)k * (CTHREADS * 4u), 4);
-#pragma unroll
-    for (int k = 0; k < CWIN / (CTHREADS * 4); k++)
-      *(uint32_t*)&win[threadIdx.x * 4u + (uint32_t)k * (CTHREADS * 4u)] = v[k];
-    if (nlen) {
-      const uint32_t pat = 0x01010101u * needle[0];
-#pragma unroll
-      for (int k = 0; k < CWIN / (CTHREADS * 4); k++) {
-        uint32_t p = threadIdx.x * 4u + (uint32_t)k * (CTHREADS * 4u);
-        if (p >= W.nbytes) continue;
-        uint32_t x = v[k] ^ pat;
-        uint32_t cand = (x - 0x01010101u) & ~x & 0x80808080u;
-        while (cand) {
-          int b = (__builtin_ctz(cand)) >> 3;
-          cand &= cand - 1;
-          uint32_t qi = atomicAdd(&qn, 1u);
-          if (qi < CQMAX) q[qi] = (uint16_t)(p + b);
-        }
-      }
-    }
-  }
-  for (uint32_t i = threadIdx.x; i < CWIN / 32; i += CTHREADS) bm[i] = 0;
-  __syncthreads();
-  if (nlen) {
-    if (qn <= CQMAX) {
-      for (uint32_t i = threadIdx.x; i < qn; i += CTHREADS) {
-        uint32_t pos = q[i];
-        if (pos + nlen <= CWIN) {
-          int k = 0;  // verify from 0: the borrow trick has false positives
-          while (k < nlen && win[pos + k] == needle[k]) k++;
-          if (k == nlen) atomicOr(&bm[pos >> 5], 1u << (pos & 31));
-        }
-      }
-    } else {  // queue overflow (pathological needle[0] density): full sweep
-      for (uint32_t p = threadIdx.x * 4u; p < W.nbytes; p += CTHREADS * 4u) {
-        uint32_t w = *(const uint32_t*)&win[p];
-        uint32_t x = w ^ pat_full(needle[0]);
-        uint32_t cand = (x - 0x01010101u) & ~x & 0x80808080u;
-        while (cand) {
-          int b = (__builtin_ctz(cand)) >> 3;
-          cand &= cand - 1;
-          uint32_t pos = p + b;
-          if (pos + nlen <= CWIN) {
-            int k = 0;
-            while (k < nlen && win[pos + k] == needle[k]) k++;
-            if (k == nlen) atomicOr(&bm[pos >> 5], 1u << (pos & 31));
-          }
-        }
-      }
-    }
-  }
-  __syncthreads();
-  const uint32_t* win32 = (const uint32_t*)win;
-  for (uint32_t i = threadIdx.x; i < W.n_values; i += CTHREADS) {
-    uint32_t o = starts_pool[W.starts + i];
-    uint32_t sh = (o & 3) * 8;
-    uint32_t vl = win32[o >> 2] >> sh;
-    if (sh) vl |= win32[(o >> 2) + 1] << (32 - sh);
-    uint8_t hit = 0;
-    if (nlen == 0) {
-      hit = 1;
-    } else if (vl >= (uint32_t)nlen) {
-      uint32_t lo = o + 4, hi = o + 4 + vl - nlen;  // inclusive starts
-      uint32_t w0 = lo >> 5, w1 = hi >> 5;
-      if (w0 == w1) {
-        uint32_t m = (hi - lo == 31) ? ~0u
-                                     : (((1u << (hi - lo + 1)) - 1) << (lo & 31));
-        hit = (bm[w0] & m) != 0;
-      } else {
-        uint32_t m0 = ~0u << (lo & 31);
-        uint32_t m1 = ((hi & 31) == 31) ? ~0u : ((1u << ((hi & 31) + 1)) - 1);
-        hit = ((bm[w0] & m0) != 0) | ((bm[w1] & m1) != 0);
-        for (uint32_t w = w0 + 1; w < w1 && !hit; w++) hit |= (bm[w] != 0);
-      }
-    }
-    uint32_t di = W.dense0 + i;
-    mask[direct ? row0 + di : rowof[row0 + di]] &= hit;
-  }
-}
-
-// k_contains_win's sibling for the substring modes it does not cover:
-// ASCII-folded (ICONTAINS) and/or negated (NOT_CONTAINS, NOT_ICONTAINS).
-// Same design — stage, register presweep into the candidate queue, verify
-// into the match-start bitmap, per-value range checks — kept as a separate
-// kernel so the plain CONTAINS instantiation stays exactly as measured.
-// FOLD: the LDS image stays EXACT (it also holds each value's u32 length
-// prefix, and a length byte in 'A'..'Z' — lengths 65-90 — must read back
-// unfolded); haystack bytes fold at the presweep (registers) and at the
-// verify compare. A presweep candidate that starts on a length byte is
-// harmless: the per-value range [o+4, o+4+vl-nlen] never includes it.
-// neg flips the hit of the value's own row; null rows were zeroed by the
-// k_def_levels launch and are never visited here.
-template <bool FOLD>
-__global__ void __launch_bounds__(CTHREADS)
-k_like_win(const uint8_t* __restrict__ dec,
-           const DevCWin* __restrict__ wins, int n,
-           const DevPage* __restrict__ pages,
-           const uint16_t* __restrict__ starts_pool,
-           const uint8_t* __restrict__ needle, int nlen, int neg,
-           const uint32_t* __restrict__ rowof, uint8_t* __restrict__ mask) {
-  __shared__ uint8_t win[CWIN];
-  __shared__ uint32_t bm[CWIN / 32];
-  __shared__ uint16_t q[CQMAX];
-  __shared__ uint32_t qn;
-  __shared__ int shit;
-  if (blockIdx.x >= (unsigned)n) return;
-  const DevCWin W = wins[blockIdx.x];
-  const DevPage pg = pages[W.page_id];
-  const uint32_t row0 = pg.row_start;
-  bool direct = true;
-  if (pg.optional) {
-    const uint8_t* ds; uint32_t dl; bool av;
-    def_levels(pg, dec + pg.dst_off, &ds, &dl, &av);
-    direct = av;
-  }
-  const uint8_t* src = dec + W.src;
-  auto hb = [](uint8_t c) -> uint8_t { return FOLD ? fold1(c) : c; };
-  if (W.nbytes > CWIN) {  // single oversized value: strided global scan
-    uint32_t vl;
-    __builtin_memcpy(&vl, src, 4);
-    if (threadIdx.x == 0) shit = (nlen == 0);
-    __syncthreads();
-    if (nlen && vl >= (uint32_t)nlen) {
-      for (uint32_t j = threadIdx.x; j + (uint32_t)nlen <= vl && !shit;
-           j += CTHREADS) {
-        int k = 0;
-        while (k < nlen && hb(src[4 + j + k]) == needle[k]) k++;
-        if (k == nlen) shit = 1;
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      uint32_t di = W.dense0;
-      mask[direct ? row0 + di : rowof[row0 + di]] &=
-          (uint8_t)((shit != 0) ^ (neg != 0));
-    }
-    return;
-  }
-  if (threadIdx.x == 0) qn = 0;
-  __syncthreads();
-  {
     uint32_t v[CWIN / (CTHREADS * 4)];
 #pragma unroll
     for (int k = 0; k < CWIN / (CTHREADS * 4); k++)
@@ -1810,13 +1693,10 @@ k_like_win(const uint8_t* __restrict__ dec,
     if (qn <= CQMAX) {
       for (uint32_t i = threadIdx.x; i < qn; i += CTHREADS) {
         uint32_t pos = q[i];
-        if (pos + nlen <= CWIN) {
-          int k = 0;
-          while (k < nlen && hb(win[pos + k]) == needle[k]) k++;
-          if (k == nlen) atomicOr(&bm[pos >> 5], 1u << (pos & 31));
-        }
+        if (pos + nlen <= CWIN && match_at(win_at, pos))
+          atomicOr(&bm[pos >> 5], 1u << (pos & 31));
       }
-    } else {  // queue overflow: full sweep from LDS
+    } else {  // queue overflow (pathological needle[0] density): full sweep
       for (uint32_t p = threadIdx.x * 4u; p < W.nbytes; p += CTHREADS * 4u) {
         uint32_t w = *(const uint32_t*)&win[p];
         uint32_t x = (FOLD ? fold4(w) : w) ^ pat_full(needle[0]);
@@ -1825,11 +1705,8 @@ k_like_win(const uint8_t* __restrict__ dec,
           int b = (__builtin_ctz(cand)) >> 3;
           cand &= cand - 1;
           uint32_t pos = p + b;
-          if (pos + nlen <= CWIN) {
-            int k = 0;
-            while (k < nlen && hb(win[pos + k]) == needle[k]) k++;
-            if (k == nlen) atomicOr(&bm[pos >> 5], 1u << (pos & 31));
-          }
+          if (pos + nlen <= CWIN && match_at(win_at, pos))
+            atomicOr(&bm[pos >> 5], 1u << (pos & 31));
         }
       }
     }
@@ -1838,9 +1715,7 @@ k_like_win(const uint8_t* __restrict__ dec,
   const uint32_t* win32 = (const uint32_t*)win;
   for (uint32_t i = threadIdx.x; i < W.n_values; i += CTHREADS) {
     uint32_t o = starts_pool[W.starts + i];
-    uint32_t sh = (o & 3) * 8;
-    uint32_t vl = win32[o >> 2] >> sh;
-    if (sh) vl |= win32[(o >> 2) + 1] << (32 - sh);
+    uint32_t vl = win_vlen(win32, o);
     uint8_t hit = 0;
     if (nlen == 0) {
       hit = 1;
@@ -1858,8 +1733,7 @@ k_like_win(const uint8_t* __restrict__ dec,
         for (uint32_t w = w0 + 1; w < w1 && !hit; w++) hit |= (bm[w] != 0);
       }
     }
-    uint32_t di = W.dense0 + i;
-    mask[direct ? row0 + di : rowof[row0 + di]] &= (uint8_t)(hit ^ (neg != 0));
+    win_mask_and(mask, rowof, direct, row0, W.dense0 + i, (uint8_t)(hit ^ NEG));
   }
 }
 
@@ -1882,12 +1756,7 @@ k_affix_win(const uint8_t* __restrict__ dec,
   const DevCWin W = wins[blockIdx.x];
   const DevPage pg = pages[W.page_id];
   const uint32_t row0 = pg.row_start;
-  bool direct = true;
-  if (pg.optional) {
-    const uint8_t* ds; uint32_t dl; bool av;
-    def_levels(pg, dec + pg.dst_off, &ds, &dl, &av);
-    direct = av;
-  }
+  const bool direct = win_direct(pg, dec);
   const uint8_t* src = dec + W.src;
   if (W.nbytes > CWIN) {  // single oversized value: compare in global memory
     uint32_t vl;
@@ -1900,11 +1769,9 @@ k_affix_win(const uint8_t* __restrict__ dec,
         if (s[k] != needle[k]) smiss = 1;
     }
     __syncthreads();
-    if (threadIdx.x == 0) {
-      uint32_t di = W.dense0;
-      mask[direct ? row0 + di : rowof[row0 + di]] &=
-          (uint8_t)((smiss == 0) ^ (neg != 0));
-    }
+    if (threadIdx.x == 0)
+      win_mask_and(mask, rowof, direct, row0, W.dense0,
+                   (uint8_t)((smiss == 0) ^ (neg != 0)));
     return;
   }
 #pragma unroll
@@ -1918,9 +1785,7 @@ k_affix_win(const uint8_t* __restrict__ dec,
   const uint32_t* win32 = (const uint32_t*)win;
   for (uint32_t i = threadIdx.x; i < W.n_values; i += CTHREADS) {
     uint32_t o = starts_pool[W.starts + i];
-    uint32_t sh = (o & 3) * 8;
-    uint32_t vl = win32[o >> 2] >> sh;
-    if (sh) vl |= win32[(o >> 2) + 1] << (32 - sh);
+    uint32_t vl = win_vlen(win32, o);
     uint8_t hit = 0;
     if (vl >= (uint32_t)nlen) {
       uint32_t b = o + 4 + (SUFFIX ? vl - (uint32_t)nlen : 0u);
@@ -1928,8 +1793,8 @@ k_affix_win(const uint8_t* __restrict__ dec,
       while (k < nlen && win[b + k] == needle[k]) k++;
       hit = (k == nlen);
     }
-    uint32_t di = W.dense0 + i;
-    mask[direct ? row0 + di : rowof[row0 + di]] &= (uint8_t)(hit ^ (neg != 0));
+    win_mask_and(mask, rowof, direct, row0, W.dense0 + i,
+                 (uint8_t)(hit ^ (neg != 0)));
   }
 }
 
@@ -2651,30 +2516,26 @@ void launch_brres_wave(hipStream_t st, uint8_t* dec, const DevBrRes* recs,
                        const DevPiece* pieces, int n) {
   if (n) hipLaunchKernelGGL(k_brres_wave, dim3(n), dim3(WAVE), 0, st, dec, recs, pieces, n);
 }
-void launch_contains_win(hipStream_t st, const uint8_t* dec,
-                         const DevCWin* wins, int n, const DevPage* pages,
-                         const uint16_t* starts_pool, const uint8_t* needle,
-                         int nlen, const uint32_t* rowof, uint8_t* mask) {
-  if (n) hipLaunchKernelGGL(k_contains_win, dim3(n), dim3(CTHREADS), 0, st, dec, wins, n, pages, starts_pool, needle, nlen, rowof, mask);
-}
-void launch_like_win(hipStream_t st, const uint8_t* dec, const DevCWin* wins,
-                     int n, const DevPage* pages, const uint16_t* starts_pool,
-                     const uint8_t* needle, int nlen, int mode,
-                     const uint32_t* rowof, uint8_t* mask) {
+void launch_str_win(hipStream_t st, const uint8_t* dec, const DevCWin* wins,
+                    int n, const DevPage* pages, const uint16_t* starts_pool,
+                    const uint8_t* needle, int nlen, int mode,
+                    const uint32_t* rowof, uint8_t* mask) {
   if (!n) return;
-  const int neg = (mode & STRF_NEG) ? 1 : 0;
-#define GPUQ_LIKE_LAUNCH(K) \
-  hipLaunchKernelGGL(K, dim3(n), dim3(CTHREADS), 0, st, dec, wins, n, pages, \
-                     starts_pool, needle, nlen, neg, rowof, mask)
+  const bool fold = mode & STRF_FOLD, neg = mode & STRF_NEG;
+  auto launch = [&](auto kern, auto... extra) {
+    hipLaunchKernelGGL(kern, dim3(n), dim3(CTHREADS), 0, st, dec, wins, n,
+                       pages, starts_pool, needle, nlen, extra..., rowof, mask);
+  };
   switch (mode & STRF_KIND) {
-    case STR_PREFIX: GPUQ_LIKE_LAUNCH(k_affix_win<false>); break;
-    case STR_SUFFIX: GPUQ_LIKE_LAUNCH(k_affix_win<true>); break;
+    case STR_PREFIX: launch(k_affix_win<false>, (int)neg); break;
+    case STR_SUFFIX: launch(k_affix_win<true>, (int)neg); break;
     default:
-      if (mode & STRF_FOLD) GPUQ_LIKE_LAUNCH(k_like_win<true>);
-      else GPUQ_LIKE_LAUNCH(k_like_win<false>);
+      if (fold && neg) launch(k_contains_win<true, true>);
+      else if (fold) launch(k_contains_win<true, false>);
+      else if (neg) launch(k_contains_win<false, true>);
+      else launch(k_contains_win<false, false>);
       break;
   }
-#undef GPUQ_LIKE_LAUNCH
 }
 void launch_null_clear_valid(hipStream_t st, const uint8_t* dec,
                              const DevPage* pages, const int32_t* ids, int n,

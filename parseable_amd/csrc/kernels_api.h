@@ -22,16 +22,13 @@ void launch_def_levels(hipStream_t, const uint8_t* dec, const DevPage*,
                        const int32_t* ids, int n, uint8_t* valid,
                        uint8_t* null_mask, uint32_t* rowof, uint32_t* rank,
                        uint32_t* present, int32_t* d_err);
-void launch_contains_win(hipStream_t, const uint8_t* dec, const DevCWin* wins,
-                         int n, const DevPage* pages,
-                         const uint16_t* starts_pool, const uint8_t* needle,
-                         int nlen, const uint32_t* rowof, uint8_t* mask);
-// the LIKE-family modes k_contains_win does not cover (mode: StrKind |
-// STRF_*, dev_types.h); the needle of a STRF_FOLD mode is lower-cased
-void launch_like_win(hipStream_t, const uint8_t* dec, const DevCWin* wins,
-                     int n, const DevPage* pages, const uint16_t* starts_pool,
-                     const uint8_t* needle, int nlen, int mode,
-                     const uint32_t* rowof, uint8_t* mask);
+// every LIKE-family mode over PLAIN-page windows (mode: StrKind | STRF_*,
+// dev_types.h): k_contains_win<FOLD, NEG> for the substring modes,
+// k_affix_win<SUFFIX> for prefix/suffix; a STRF_FOLD needle is lower-cased
+void launch_str_win(hipStream_t, const uint8_t* dec, const DevCWin* wins,
+                    int n, const DevPage* pages, const uint16_t* starts_pool,
+                    const uint8_t* needle, int nlen, int mode,
+                    const uint32_t* rowof, uint8_t* mask);
 // IS NULL: clear the valid rows of the listed pages from the mask (after
 // launch_def_levels wrote `valid` for their null-bearing pages)
 void launch_null_clear_valid(hipStream_t, const uint8_t* dec, const DevPage*,

@@ -548,23 +548,27 @@ Lz4Plan lz4_walk(const uint8_t* src, size_t comp, size_t uncomp,
   };
   auto defer_match = [&](size_t dst, size_t off, size_t ml) {
     plan.backrefs.push_back({(uint32_t)dst, (uint32_t)(dst - off), (uint32_t)ml});
+    uint32_t ps = 0, pn = 0;
     if (!plan.fallback) {
       uint32_t pat = (uint32_t)std::min(off, ml);
       std::vector<Lz4Piece> pieces;
       if (resolve((uint32_t)(dst - off), (uint32_t)(dst - off + pat), pieces)) {
-        uint32_t ps = (uint32_t)plan.pieces.size();
+        ps = (uint32_t)plan.pieces.size();
+        pn = (uint32_t)pieces.size();
         plan.pieces.insert(plan.pieces.end(), pieces.begin(), pieces.end());
         plan.resolved.push_back({(uint32_t)dst, (uint32_t)ml, (uint32_t)off,
-                                 ps, (uint32_t)pieces.size()});
-        // insert map entry (records arrive in ascending dst order)
-        M.push_back({(uint32_t)dst, (uint32_t)ml, (uint32_t)off, ps,
-                     (uint32_t)pieces.size()});
+                                 ps, pn});
       } else {
         plan.fallback = true;
         plan.resolved.clear();
         plan.pieces.clear();
       }
     }
+    // insert map entry (records arrive in ascending dst order). After a
+    // fallback too: its pieces are never read again, but overlaps_gap must
+    // keep seeing the gap, or a later in-segment match that reads it would
+    // run in phase 1 on unwritten bytes instead of being deferred
+    M.push_back({(uint32_t)dst, (uint32_t)ml, (uint32_t)off, ps, pn});
   };
 
   auto close_segment = [&](size_t end_s, size_t end_d, bool big) {

@@ -1,4 +1,4 @@
-"""LIKE-family (icontains / starts_with / ends_with / not_*) and
+"""LIKE-family (contains / icontains / starts_with / ends_with / not_*) and
 is_null / is_not_null predicates on the GPU: the window kernels over PLAIN
 pages, the per-dict-entry LUT, k_cmp_str on hash-mode columns, and the
 def-level null task. Expected values come from tests/strpred_common.py
@@ -85,7 +85,7 @@ def _pred(col, op, lit=None):
     return p
 
 
-@pytest.mark.parametrize("op", sc.NEW_STR_OPS)
+@pytest.mark.parametrize("op", sc.STR_OPS)
 def test_window_and_lut(c6, session, capfd, op):
     for lit in NEEDLES:
         q = {"select": COUNT, "preds": [_pred("message", op, lit)]}
@@ -100,7 +100,7 @@ def test_window_and_lut(c6, session, capfd, op):
             assert rows == [[n_nonnull if all_rows else 0]], (op, lit, rows)
 
 
-@pytest.mark.parametrize("op", sc.NEW_STR_OPS)
+@pytest.mark.parametrize("op", sc.STR_OPS)
 def test_lut_only(c6, session, capfd, op):
     for lit in sc.level_needles(op):
         q = {"select": [{"agg": "count_star"},
@@ -168,6 +168,8 @@ def test_oversized_value(c6, session, capfd):
     for preds in (
         [_pred("message", "starts_with", "Error"),
          _pred("message", "ends_with", "TIMEOUT")],
+        [_pred("message", "contains", "TIMEOUT")],
+        [_pred("message", "not_contains", "TIMEOUT")],
         [_pred("message", "icontains", "timeout")],
         [_pred("message", "not_icontains", "TIMEOUT")],
         [_pred("message", "not_starts_with", "Error")],
@@ -185,6 +187,32 @@ def test_oversized_value(c6, session, capfd):
          "time_range": tr}
     assert sc.selected(data, q) == big
     _check(c6, session, q, capfd)
+
+
+@pytest.mark.parametrize(
+    "op", ["contains", "icontains", "not_contains", "not_icontains"])
+def test_queue_overflow(c6, session, capfd, op):
+    """File 1 holds a run of messages that are nearly all '=': a window
+    inside it has far more than the 4,096 candidate positions the substring
+    kernel queues for a needle starting with '=', so the kernel drops the
+    queue and sweeps the staged window."""
+    data = c6["data"]
+    msg = data["message"]
+    run = [i for i, v in enumerate(msg)
+           if v is not None and v.startswith(b"=" * 120)]
+    # contiguous, >= three windows of [u32 len][bytes] records, >= 90 % '=':
+    # whatever the window and page alignment, some window lies inside the
+    # run and holds > 0.9 * (16384 - one record) candidates
+    assert run == list(range(run[0], run[0] + len(run)))
+    assert {data["__file"][i] for i in run} == {1}
+    n_bytes = sum(4 + len(msg[i]) for i in run)
+    assert n_bytes >= 3 * 16384
+    assert sum(msg[i].count(b"=") for i in run) >= 0.9 * n_bytes
+    for lit in ("=Error", "=error", "==", "=x"):
+        q = {"select": COUNT, "preds": [_pred("message", op, lit)],
+             "time_range": [BASE + MIN, BASE + 2 * MIN]}
+        _, paths, _ = _check(c6, session, q, capfd)
+        assert paths == [("0", "message", op, "lut+window")], paths
 
 
 @pytest.mark.parametrize("op", sc.NULL_OPS)
