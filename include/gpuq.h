@@ -233,6 +233,72 @@ void gpuq_plan_destroy(gpuq_plan*);
  * callers on GPU hosts must treat failure as fatal, never fall back). */
 int32_t gpuq_device_count(void);
 
+/* ---- test support (NOT part of the drop-in surface) ------------------ */
+
+/* Runs the page-decompression planning of gpuq_plan_build and the
+ * decompress launches of gpuq_plan_execute on caller-supplied compressed
+ * blocks, so a test can compare the decompressed arena byte for byte with
+ * an independent decoder and see which path every page took. */
+
+typedef struct {
+  int32_t codec;            /* parquet codec id: 0 uncompressed, 1 snappy,
+                               7 LZ4_RAW */
+  const uint8_t* comp;      /* compressed block */
+  uint32_t comp_len;
+  uint32_t uncomp_len;      /* the page header's uncompressed size */
+} gpuq_decomp_page;
+
+/* plan mode (low byte of `mode`) */
+enum {
+  GPUQ_DECOMP_AUTO = 0,         /* what plan build chooses */
+  GPUQ_DECOMP_FORCE_SEGMENT,    /* segment plan, litpar heuristic off */
+  GPUQ_DECOMP_FORCE_LITPAR,     /* litpar plan when its walk succeeds, else
+                                   the segment plan (as AUTO does) */
+  GPUQ_DECOMP_FORCE_FALLBACK    /* segment plan + serial windowed resolver */
+};
+/* or'ed onto the plan mode: no device work, no session needed. `out` gets
+ * the host scalar decoders' bytes; with REPLAY it gets a serial host replay
+ * of the planned device records instead (segments, literal copies, inline /
+ * resolved / windowed matches, in launch order). */
+#define GPUQ_DECOMP_HOST_ONLY   0x100
+#define GPUQ_DECOMP_HOST_REPLAY 0x200
+
+/* path a page took (gpuq_decomp_stats.mode) */
+enum {
+  GPUQ_DECOMP_PAGE_SEGMENT = 0, /* segments + literal-resolved records */
+  GPUQ_DECOMP_PAGE_LITPAR,      /* literal records + resolved records */
+  GPUQ_DECOMP_PAGE_FALLBACK,    /* segments + serial windowed backrefs */
+  GPUQ_DECOMP_PAGE_RAW,         /* stored uncompressed: plain copy */
+  GPUQ_DECOMP_PAGE_HOST_IMAGE   /* host-decompressed image staged directly */
+};
+
+typedef struct {
+  int32_t mode;                 /* GPUQ_DECOMP_PAGE_* */
+  uint32_t n_seq;               /* sequences (snappy: elements) walked */
+  uint32_t n_segs, n_big;       /* segments; of those, giant single-sequence */
+  uint32_t n_lit_lane, n_lit_wave;
+  uint32_t n_inl;               /* host-inlined pattern records */
+  uint32_t n_res_lane, n_res_wave;
+  uint32_t n_pieces;
+  uint32_t n_backrefs, n_far;   /* windowed records; of those, far branch */
+} gpuq_decomp_stats;
+
+/* The blocks are packed back to back into the raw buffer after `raw_lead`
+ * (0..15) pad bytes. The decompressed arena is laid out as plan build lays
+ * it out: every image starts 16-aligned, and the over-read pad follows the
+ * last image. The whole arena is filled with `sentinel` before any kernel
+ * runs, so the padding between images and the trailing pad double as guard
+ * regions; *guard_len is the size of the trailing one, *arena_len the bytes
+ * written to `out` (images + padding + guard). stats has n_pages entries.
+ * *d_err receives the kernels' error word (0 in host-only modes). A stream
+ * the host walk rejects is an error (-1, message via gpuq_last_error — with
+ * a NULL session, gpuq_last_error(NULL)) and nothing is launched. */
+int32_t gpuq_test_decompress(gpuq_ctx*, const gpuq_decomp_page* pages,
+                             int32_t n_pages, int32_t raw_lead, int32_t mode,
+                             uint8_t sentinel, uint8_t* out, uint64_t out_cap,
+                             uint64_t* arena_len, uint64_t* guard_len,
+                             gpuq_decomp_stats* stats, int32_t* d_err);
+
 #ifdef __cplusplus
 }
 #endif

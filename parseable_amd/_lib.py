@@ -52,6 +52,32 @@ class GpuqMetrics(C.Structure):
     ]
 
 
+class GpuqDecompPage(C.Structure):
+    """Test support (gpuq_test_decompress): one compressed block."""
+    _fields_ = [
+        ("codec", C.c_int32),
+        ("comp", C.c_void_p),
+        ("comp_len", C.c_uint32),
+        ("uncomp_len", C.c_uint32),
+    ]
+
+
+class GpuqDecompStats(C.Structure):
+    """Test support: the path a page took and its record counts."""
+    _fields_ = [("mode", C.c_int32)] + [
+        (n, C.c_uint32) for n in (
+            "n_seq", "n_segs", "n_big", "n_lit_lane", "n_lit_wave", "n_inl",
+            "n_res_lane", "n_res_wave", "n_pieces", "n_backrefs", "n_far")
+    ]
+
+
+# gpuq_test_decompress plan modes / flags and per-page paths (include/gpuq.h)
+DECOMP_MODES = {"auto": 0, "segment": 1, "litpar": 2, "fallback": 3}
+DECOMP_HOST_ONLY = 0x100
+DECOMP_HOST_REPLAY = 0x200
+DECOMP_PATHS = ("segment", "litpar", "fallback", "raw", "host_image")
+CODECS = {"uncompressed": 0, "snappy": 1, "lz4_raw": 7}
+
 OPS = {"eq": 0, "ne": 1, "lt": 2, "le": 3, "gt": 4, "ge": 5, "between": 6, "contains": 7,
        "icontains": 8, "starts_with": 9, "ends_with": 10, "not_contains": 11,
        "not_icontains": 12, "not_starts_with": 13, "not_ends_with": 14,
@@ -109,9 +135,55 @@ def load():
     lib.gpuq_plan_metrics.restype = C.c_int32
     lib.gpuq_plan_metrics.argtypes = [C.c_void_p, C.POINTER(GpuqMetrics)]
     lib.gpuq_plan_destroy.argtypes = [C.c_void_p]
+    lib.gpuq_test_decompress.restype = C.c_int32
+    lib.gpuq_test_decompress.argtypes = [
+        C.c_void_p, C.POINTER(GpuqDecompPage), C.c_int32, C.c_int32, C.c_int32,
+        C.c_uint8, C.c_void_p, C.c_uint64,
+        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+        C.POINTER(GpuqDecompStats), C.POINTER(C.c_int32),
+    ]
     _lib = lib
     return lib
 
 
 def device_count() -> int:
     return load().gpuq_device_count()
+
+
+def decompress_pages(pages, mode="auto", raw_lead=0, host=None, session=None,
+                     sentinel=0xA5):
+    """Test support: run the page-decompression planner (and, with a session
+    handle, the decompress kernels) on compressed blocks.
+
+    pages: [(codec name, compressed bytes, uncompressed length)].
+    host: None (device; needs `session`, a gpuq_ctx handle), "decode" (the
+    host scalar decoders) or "replay" (serial host replay of the planned
+    records). Returns (arena bytes, [stats dict per page], guard_len, d_err);
+    raises RuntimeError with the library's message when it refuses."""
+    lib = load()
+    n = len(pages)
+    arr = (GpuqDecompPage * max(n, 1))()
+    keep = []
+    cap = 16384 + 64
+    for i, (codec, comp, uncomp) in enumerate(pages):
+        buf = C.create_string_buffer(bytes(comp), max(len(comp), 1))
+        keep.append(buf)
+        arr[i] = GpuqDecompPage(CODECS[codec], C.addressof(buf), len(comp), uncomp)
+        cap += (uncomp + 15) & ~15
+    flags = DECOMP_MODES[mode] | {None: 0, "decode": DECOMP_HOST_ONLY,
+                                  "replay": DECOMP_HOST_REPLAY}[host]
+    out = C.create_string_buffer(cap)
+    arena_len, guard_len, d_err = C.c_uint64(), C.c_uint64(), C.c_int32()
+    stats = (GpuqDecompStats * max(n, 1))()
+    rc = lib.gpuq_test_decompress(
+        session if host is None else None, arr, n, raw_lead, flags, sentinel,
+        out, cap, C.byref(arena_len), C.byref(guard_len), stats, C.byref(d_err))
+    if rc != 0:
+        msg = lib.gpuq_last_error(session if host is None else None)
+        raise RuntimeError(msg.decode(errors="replace"))
+    st = []
+    for i in range(n):
+        d = {f: getattr(stats[i], f) for f, _ in GpuqDecompStats._fields_}
+        d["mode"] = DECOMP_PATHS[d["mode"]]
+        st.append(d)
+    return out.raw[:arena_len.value], st, guard_len.value, d_err.value

@@ -428,8 +428,12 @@ extern "C" gpuq_ctx* gpuq_session_create(uint64_t device_mask) {
   return c;
 }
 extern "C" void gpuq_session_destroy(gpuq_ctx* c) { delete c; }
+namespace {
+// error text of calls made without a session (test-support entry only)
+thread_local std::string g_null_ctx_error = "null ctx";
+}  // namespace
 extern "C" const char* gpuq_last_error(gpuq_ctx* c) {
-  return c ? c->last_error.c_str() : "null ctx";
+  return c ? c->last_error.c_str() : g_null_ctx_error.c_str();
 }
 extern "C" int32_t gpuq_device_count(void) {
   int n = 0;
@@ -772,6 +776,220 @@ void Ring::copy_spans(uint8_t* d_dst, const std::vector<Span>& spans) {
 }
 void Ring::copy(void* d_dst, const void* src, size_t len) {
   if (len) copy_spans((uint8_t*)d_dst, {{(const uint8_t*)src, len}});
+}
+
+// ------------------------------------------------------------------
+// page decompression planning + launches (shared by plan build / execute
+// and the gpuq_test_decompress test-support entry)
+// ------------------------------------------------------------------
+// device record vectors one planning unit (chunk) fills
+struct DecompRecs {
+  std::vector<DevSeg> segs;
+  std::vector<DevBr> brs;
+  std::vector<DevPageBr> pagebrs;
+  std::vector<DevBrRes> res_lane, res_wave;
+  std::vector<DevPiece> piece_pool;
+  std::vector<DevBrInl> brinl;
+  std::vector<DevLit> lits_lane, lits_wave;
+  // host-decompressed page images staged straight into the dec arena
+  // (snappy piece-explosion fallback — no serial snappy device kernel)
+  std::vector<std::pair<uint64_t, std::vector<uint8_t>>> himgs;
+};
+
+constexpr uint32_t BR_FAR = 16384 / 2;  // kernels.hip BR_WIN / 2
+
+// decompress planning for one page image (data or hash-col dict):
+// segment walk + litpar/backref records, exactly the round-1 logic.
+// force: GPUQ_DECOMP_* plan mode (plan build passes AUTO); st (optional)
+// receives the path taken and the record counts.
+void plan_decomp_page(DecompRecs& cb, int codec, const uint8_t* praw,
+                      uint64_t src_abs, uint64_t dst_abs, uint32_t comp,
+                      uint32_t uncomp, bool raw_page,
+                      int force = GPUQ_DECOMP_AUTO,
+                      gpuq_decomp_stats* st = nullptr) {
+  Lz4Plan lp;
+  if (st) *st = gpuq_decomp_stats{};
+  if (!raw_page && codec == CODEC_SNAPPY) {
+    lp = snappy_walk(praw, comp, uncomp);
+    if (st) st->n_seq = lp.n_seq;
+    if (lp.fallback) {
+      // piece explosion (rare): host-decompress the page and stage
+      // its image straight into the dec arena at load
+      std::vector<uint8_t> img(uncomp);
+      if (snappy_decompress_host(praw, comp, img.data(), uncomp) !=
+          (int)uncomp)
+        throw std::runtime_error("snappy page decode failure");
+      cb.himgs.emplace_back(dst_abs, std::move(img));
+      if (st) st->mode = GPUQ_DECOMP_PAGE_HOST_IMAGE;
+      return;
+    }
+  } else if (!raw_page) {
+    // test knob: exercise the serial windowed fallback kernel on
+    // arbitrary content
+    static const bool env_fb =
+        std::getenv("GPUQ_FORCE_LZ4_FALLBACK") != nullptr;
+    const bool force_fb = force == GPUQ_DECOMP_FORCE_FALLBACK ||
+                          (force == GPUQ_DECOMP_AUTO && env_fb);
+    try {
+      lp = lz4_walk(praw, comp, uncomp, 8192);
+      if (force_fb) {
+        lp.fallback = true;
+        lp.resolved.clear();
+        lp.pieces.clear();
+      }
+      // dense short-sequence pages (LZ4 over near-random dict
+      // indices) degenerate the segment kernel into a serial token
+      // parse — switch those to the all-literal/all-resolved plan
+      const bool want_litpar =
+          force == GPUQ_DECOMP_FORCE_LITPAR ||
+          (force == GPUQ_DECOMP_AUTO && lp.n_seq >= 256 &&
+           uncomp / lp.n_seq < 96);
+      if (!lp.fallback && want_litpar) {
+        Lz4Plan lp2 = lz4_walk(praw, comp, uncomp, 8192, /*litpar=*/true);
+        if (!lp2.fallback) lp = std::move(lp2);
+      }
+    } catch (const std::exception&) {
+      if (comp == uncomp) raw_page = true;  // stored raw
+      else throw;
+    }
+    if (st) st->n_seq = lp.n_seq;
+  }
+  if (raw_page) {
+    DevSeg sgl{};
+    sgl.src_off = src_abs;
+    sgl.dst_off = dst_abs;
+    sgl.comp_len = comp;
+    sgl.out_len = uncomp;
+    sgl.raw = 1;
+    cb.segs.push_back(sgl);
+    if (st) {
+      st->mode = GPUQ_DECOMP_PAGE_RAW;
+      st->n_seq = 0;
+      st->n_segs = 1;
+    }
+    return;
+  }
+  if (st) {
+    st->mode = lp.fallback ? GPUQ_DECOMP_PAGE_FALLBACK
+               : lp.litpar ? GPUQ_DECOMP_PAGE_LITPAR
+                           : GPUQ_DECOMP_PAGE_SEGMENT;
+    st->n_segs = (uint32_t)lp.segs.size();
+    for (const auto& sg : lp.segs) st->n_big += sg.big != 0;
+  }
+  for (const auto& sg : lp.segs) {
+    DevSeg d2{};
+    d2.src_off = src_abs + sg.s_off;
+    d2.dst_off = dst_abs + sg.d_off;
+    d2.comp_len = sg.comp_len;
+    d2.out_len = sg.out_len;
+    d2.big = sg.big;
+    cb.segs.push_back(d2);
+  }
+  for (const auto& lt : lp.lits) {
+    DevLit dl{(src_abs + lt.src) | ((uint64_t)lt.len << 40),
+              dst_abs + lt.dst};
+    (lt.len <= 256 ? cb.lits_lane : cb.lits_wave).push_back(dl);
+    if (st) (lt.len <= 256 ? st->n_lit_lane : st->n_lit_wave)++;
+  }
+  if (lp.fallback) {
+    // piece explosion: serial windowed wave per page
+    DevPageBr pb{(uint32_t)cb.brs.size(), (uint32_t)lp.backrefs.size()};
+    cb.pagebrs.push_back(pb);
+    for (const auto& br : lp.backrefs) {
+      cb.brs.push_back({dst_abs + br.dst, dst_abs + br.src, br.len, 0});
+      if (st) {
+        st->n_backrefs++;
+        st->n_far += (br.dst - br.src) + br.len > BR_FAR;
+      }
+    }
+  } else if (!lp.resolved.empty()) {
+    // litpar pieces are literal-backed: the host can read any
+    // pattern of <= 8 bytes straight from the compressed stream
+    // and inline it — the resolver then never touches dec sources
+    auto lit_bytes = [&](uint32_t src, uint32_t len,
+                         uint8_t* out) -> bool {
+      const auto& Ls = lp.lits;   // dst-ascending by construction
+      size_t lo = 0, hi = Ls.size();
+      while (lo < hi) {
+        size_t mid = (lo + hi) / 2;
+        if (Ls[mid].dst <= src) lo = mid + 1;
+        else hi = mid;
+      }
+      if (lo == 0) return false;
+      const Lz4Lit& L = Ls[lo - 1];
+      if (src < L.dst || src + len > L.dst + L.len) return false;
+      std::memcpy(out, praw + L.src + (src - L.dst), len);
+      return true;
+    };
+    for (const auto& rr : lp.resolved) {
+      uint32_t pat_len = 0;
+      for (uint32_t k = 0; k < rr.piece_n; k++)
+        pat_len += lp.pieces[rr.piece_start + k].len;
+      if (lp.litpar && pat_len > 0 && pat_len <= 8 && rr.len <= 256) {
+        uint8_t buf[8] = {0};
+        uint32_t o = 0;
+        bool ok = true;
+        for (uint32_t k = 0; k < rr.piece_n && ok; k++) {
+          const Lz4Piece& pc = lp.pieces[rr.piece_start + k];
+          ok = lit_bytes(pc.src, pc.len, buf + o);
+          o += pc.len;
+        }
+        if (ok) {
+          uint64_t pat;
+          std::memcpy(&pat, buf, 8);
+          cb.brinl.push_back({(dst_abs + rr.dst) |
+                                  ((uint64_t)rr.len << 40) |
+                                  ((uint64_t)pat_len << 52),
+                              pat});
+          if (st) st->n_inl++;
+          continue;
+        }
+      }
+      uint32_t ps = (uint32_t)cb.piece_pool.size();
+      for (uint32_t k = 0; k < rr.piece_n; k++) {
+        const Lz4Piece& pc = lp.pieces[rr.piece_start + k];
+        cb.piece_pool.push_back({dst_abs + pc.src, pc.len, 0});
+      }
+      DevBrRes rec{dst_abs + rr.dst, rr.len, rr.off, ps, rr.piece_n};
+      if (rr.len <= 256) cb.res_lane.push_back(rec);
+      else cb.res_wave.push_back(rec);
+      if (st) {
+        (rr.len <= 256 ? st->n_res_lane : st->n_res_wave)++;
+        st->n_pieces += rr.piece_n;
+      }
+    }
+  }
+}
+
+// device-side view of the decompress records, in launch order
+struct DecompDev {
+  const uint8_t* d_raw;
+  uint8_t* d_dec;
+  const DevSeg* d_segs; int n_segs;
+  const DevLit* d_lits_lane; int64_t n_lits_lane;
+  const DevLit* d_lits_wave; int n_lits_wave;
+  const DevBrInl* d_brinl; int64_t n_brinl;
+  const DevBrRes* d_res_lane; int64_t n_res_lane;
+  const DevBrRes* d_res_wave; int n_res_wave;
+  const DevPiece* d_piece_pool;
+  const DevBr* d_brs;
+  const DevPageBr* d_pagebrs; int n_pagebrs;
+  int32_t* d_err;
+};
+
+// decompress: parallel segments, then ordered backref resolution
+void launch_decompress(hipStream_t st, const DecompDev& d) {
+  launch_lz4_seg(st, d.d_raw, d.d_dec, d.d_segs, d.n_segs, d.d_err);
+  // litpar pages: flat literal copies (independent of the segment pass)
+  launch_lit_lane(st, d.d_raw, d.d_dec, d.d_lits_lane, d.n_lits_lane);
+  launch_lit_wave(st, d.d_raw, d.d_dec, d.d_lits_wave, d.n_lits_wave);
+  // deferred-match resolution: host-resolved records are independent —
+  // one launch each (kernel boundary after phase 1 gives coherence);
+  // piece-explosion pages fall back to the serial windowed wave
+  launch_brres_inl(st, d.d_dec, d.d_brinl, d.n_brinl);
+  launch_brres_lane(st, d.d_dec, d.d_res_lane, d.d_piece_pool, d.n_res_lane);
+  launch_brres_wave(st, d.d_dec, d.d_res_wave, d.d_piece_pool, d.n_res_wave);
+  launch_lz4_backrefs(st, d.d_dec, d.d_brs, d.d_pagebrs, d.n_pagebrs);
 }
 
 }  // namespace
@@ -1390,20 +1608,10 @@ extern "C" gpuq_plan* gpuq_plan_build(
       int col;
     };
     std::vector<CItem> citems;
-    struct CB {
+    struct CB : DecompRecs {
       std::vector<DevPage> pages;
       std::map<std::pair<int,int>, std::vector<int32_t>> tasks;
-      std::vector<DevSeg> segs;
-      std::vector<DevBr> brs;
-      std::vector<DevPageBr> pagebrs;
-      std::vector<DevBrRes> res_lane, res_wave;
-      std::vector<DevPiece> piece_pool;
-      std::vector<DevBrInl> brinl;
-      std::vector<DevLit> lits_lane, lits_wave;
       std::vector<CItem> citems;
-      // host-decompressed page images staged straight into the dec arena
-      // (snappy piece-explosion fallback — no serial snappy device kernel)
-      std::vector<std::pair<uint64_t, std::vector<uint8_t>>> himgs;
     };
     std::vector<CB> cbs(part.chunks.size());
     parallel_for(part.chunks.size(), [&](size_t ti) {
@@ -1418,132 +1626,13 @@ extern "C" gpuq_plan* gpuq_plan_build(
       int32_t page_id = bases[ti].pid;
       const uint32_t rstart = stubs[ti].rstart;
 
-      // decompress planning for one page image (data or hash-col dict):
-      // segment walk + litpar/backref records, exactly the round-1 logic
+      // decompress planning for one page image (data or hash-col dict)
       const int chunk_codec = t.cm->codec;
       auto plan_decomp = [&](const uint8_t* praw, uint64_t src_abs,
                              uint64_t dst_abs, uint32_t comp, uint32_t uncomp,
                              bool raw_page) {
-        Lz4Plan lp;
-        if (!raw_page && chunk_codec == CODEC_SNAPPY) {
-          lp = snappy_walk(praw, comp, uncomp);
-          if (lp.fallback) {
-            // piece explosion (rare): host-decompress the page and stage
-            // its image straight into the dec arena at load
-            std::vector<uint8_t> img(uncomp);
-            if (snappy_decompress_host(praw, comp, img.data(), uncomp) !=
-                (int)uncomp)
-              throw std::runtime_error("snappy page decode failure");
-            cb.himgs.emplace_back(dst_abs, std::move(img));
-            return;
-          }
-        } else if (!raw_page) {
-          // test knob: exercise the serial windowed fallback kernel on
-          // arbitrary content (no organic fixture produces a
-          // piece-explosion page)
-          static const bool force_fb =
-              std::getenv("GPUQ_FORCE_LZ4_FALLBACK") != nullptr;
-          try {
-            lp = lz4_walk(praw, comp, uncomp, 8192);
-            if (force_fb) {
-              lp.fallback = true;
-              lp.resolved.clear();
-              lp.pieces.clear();
-            }
-            // dense short-sequence pages (LZ4 over near-random dict
-            // indices) degenerate the segment kernel into a serial token
-            // parse — switch those to the all-literal/all-resolved plan
-            if (!lp.fallback && lp.n_seq >= 256 && uncomp / lp.n_seq < 96) {
-              Lz4Plan lp2 = lz4_walk(praw, comp, uncomp, 8192, /*litpar=*/true);
-              if (!lp2.fallback) lp = std::move(lp2);
-            }
-          } catch (const std::exception&) {
-            if (comp == uncomp) raw_page = true;  // stored raw
-            else throw;
-          }
-        }
-        if (raw_page) {
-          DevSeg sgl{};
-          sgl.src_off = src_abs;
-          sgl.dst_off = dst_abs;
-          sgl.comp_len = comp;
-          sgl.out_len = uncomp;
-          sgl.raw = 1;
-          cb.segs.push_back(sgl);
-          return;
-        }
-        for (const auto& sg : lp.segs) {
-          DevSeg d2{};
-          d2.src_off = src_abs + sg.s_off;
-          d2.dst_off = dst_abs + sg.d_off;
-          d2.comp_len = sg.comp_len;
-          d2.out_len = sg.out_len;
-          d2.big = sg.big;
-          cb.segs.push_back(d2);
-        }
-        for (const auto& lt : lp.lits) {
-          DevLit dl{(src_abs + lt.src) | ((uint64_t)lt.len << 40),
-                    dst_abs + lt.dst};
-          (lt.len <= 256 ? cb.lits_lane : cb.lits_wave).push_back(dl);
-        }
-        if (lp.fallback) {
-          // piece explosion: serial windowed wave per page
-          DevPageBr pb{(uint32_t)cb.brs.size(), (uint32_t)lp.backrefs.size()};
-          cb.pagebrs.push_back(pb);
-          for (const auto& br : lp.backrefs)
-            cb.brs.push_back({dst_abs + br.dst, dst_abs + br.src, br.len, 0});
-        } else if (!lp.resolved.empty()) {
-          // litpar pieces are literal-backed: the host can read any
-          // pattern of <= 8 bytes straight from the compressed stream
-          // and inline it — the resolver then never touches dec sources
-          auto lit_bytes = [&](uint32_t src, uint32_t len,
-                               uint8_t* out) -> bool {
-            const auto& Ls = lp.lits;   // dst-ascending by construction
-            size_t lo = 0, hi = Ls.size();
-            while (lo < hi) {
-              size_t mid = (lo + hi) / 2;
-              if (Ls[mid].dst <= src) lo = mid + 1;
-              else hi = mid;
-            }
-            if (lo == 0) return false;
-            const Lz4Lit& L = Ls[lo - 1];
-            if (src < L.dst || src + len > L.dst + L.len) return false;
-            std::memcpy(out, praw + L.src + (src - L.dst), len);
-            return true;
-          };
-          for (const auto& rr : lp.resolved) {
-            uint32_t pat_len = 0;
-            for (uint32_t k = 0; k < rr.piece_n; k++)
-              pat_len += lp.pieces[rr.piece_start + k].len;
-            if (lp.litpar && pat_len > 0 && pat_len <= 8 && rr.len <= 256) {
-              uint8_t buf[8] = {0};
-              uint32_t o = 0;
-              bool ok = true;
-              for (uint32_t k = 0; k < rr.piece_n && ok; k++) {
-                const Lz4Piece& pc = lp.pieces[rr.piece_start + k];
-                ok = lit_bytes(pc.src, pc.len, buf + o);
-                o += pc.len;
-              }
-              if (ok) {
-                uint64_t pat;
-                std::memcpy(&pat, buf, 8);
-                cb.brinl.push_back({(dst_abs + rr.dst) |
-                                        ((uint64_t)rr.len << 40) |
-                                        ((uint64_t)pat_len << 52),
-                                    pat});
-                continue;
-              }
-            }
-            uint32_t ps = (uint32_t)cb.piece_pool.size();
-            for (uint32_t k = 0; k < rr.piece_n; k++) {
-              const Lz4Piece& pc = lp.pieces[rr.piece_start + k];
-              cb.piece_pool.push_back({dst_abs + pc.src, pc.len, 0});
-            }
-            DevBrRes rec{dst_abs + rr.dst, rr.len, rr.off, ps, rr.piece_n};
-            if (rr.len <= 256) cb.res_lane.push_back(rec);
-            else cb.res_wave.push_back(rec);
-          }
-        }
+        plan_decomp_page(cb, chunk_codec, praw, src_abs, dst_abs, comp, uncomp,
+                         raw_page);
       };
 
       // hash-mode dict page: decompress its image into the reserved slot
@@ -2803,23 +2892,17 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
 
   HIP_TRY(hipEventRecord(ev0, st));
   // 1. decompress: parallel segments, then ordered backref resolution
-  launch_lz4_seg(st, part.d_raw, part.d_dec, part.d_segs,
-                 (int)part.segs.size(), part.d_err);
-  // litpar pages: flat literal copies (independent of the segment pass)
-  launch_lit_lane(st, part.d_raw, part.d_dec, part.d_lits_lane,
-                  (int64_t)part.lits_lane.size());
-  launch_lit_wave(st, part.d_raw, part.d_dec, part.d_lits_wave,
-                  (int)part.lits_wave.size());
-  // deferred-match resolution: host-resolved records are independent —
-  // one launch each (kernel boundary after phase 1 gives coherence);
-  // piece-explosion pages fall back to the serial windowed wave
-  launch_brres_inl(st, part.d_dec, part.d_brinl, (int64_t)part.brinl.size());
-  launch_brres_lane(st, part.d_dec, part.d_res_lane, part.d_piece_pool,
-                    (int64_t)part.res_lane.size());
-  launch_brres_wave(st, part.d_dec, part.d_res_wave, part.d_piece_pool,
-                    (int)part.res_wave.size());
-  launch_lz4_backrefs(st, part.d_dec, part.d_brs, part.d_pagebrs,
-                      (int)part.pagebrs.size());
+  // (launch_decompress, shared with the test-support entry)
+  launch_decompress(st, DecompDev{
+      part.d_raw, part.d_dec,
+      part.d_segs, (int)part.segs.size(),
+      part.d_lits_lane, (int64_t)part.lits_lane.size(),
+      part.d_lits_wave, (int)part.lits_wave.size(),
+      part.d_brinl, (int64_t)part.brinl.size(),
+      part.d_res_lane, (int64_t)part.res_lane.size(),
+      part.d_res_wave, (int)part.res_wave.size(),
+      part.d_piece_pool, part.d_brs,
+      part.d_pagebrs, (int)part.pagebrs.size(), part.d_err});
   HIP_TRY(hipEventRecord(ev_decomp, st));
 
   // 2. decode + predicate kernels (or the fused count path)
@@ -3644,3 +3727,263 @@ gpuq_plan::~gpuq_plan() {
 }
 
 extern "C" void gpuq_plan_destroy(gpuq_plan* p) { delete p; }
+
+// ------------------------------------------------------------------
+// test support: decompress caller-supplied blocks (include/gpuq.h)
+// ------------------------------------------------------------------
+namespace {
+
+constexpr uint64_t DEC_PAD = 16384 + 64;  // plan build's over-read pad
+constexpr uint64_t RAW_SLACK = 8192;      // gpuq_plan_load's d_raw slack
+
+// serial host replay of the planned records over a host arena, one loop per
+// kernel, in launch order. Deferred-match gaps in a segment are left alone
+// (the kernel flushes arbitrary LDS bytes there), so an unresolved gap
+// keeps the caller's sentinel.
+void replay_decompress(const uint8_t* raw, uint8_t* dec, const DecompRecs& R) {
+  for (const DevSeg& sg : R.segs) {
+    const uint8_t* src = raw + sg.src_off;
+    uint8_t* dst = dec + sg.dst_off;
+    if (sg.raw) {
+      std::memcpy(dst, src, sg.out_len);
+      continue;
+    }
+    uint32_t s = 0, d = 0;
+    while (s < sg.comp_len && d < sg.out_len) {
+      uint32_t token = src[s++];
+      uint32_t lit = token >> 4;
+      if (lit == 15) {
+        uint32_t b;
+        do { b = src[s++]; lit += b; } while (b == 255);
+      }
+      if (s + lit > sg.comp_len || d + lit > sg.out_len)
+        throw std::runtime_error("replay: segment literal overrun");
+      std::memcpy(dst + d, src + s, lit);
+      s += lit;
+      d += lit;
+      if (s >= sg.comp_len) break;
+      uint32_t off = src[s] | ((uint32_t)src[s + 1] << 8);
+      s += 2;
+      uint32_t ml = token & 0xf;
+      if (ml == 15) {
+        uint32_t b;
+        do { b = src[s++]; ml += b; } while (b == 255);
+      }
+      ml += 4;
+      if (d + ml > sg.out_len)
+        throw std::runtime_error("replay: segment match overrun");
+      if (!sg.big && off <= d)
+        for (uint32_t i = 0; i < ml; i++) dst[d + i] = dst[d + i - off];
+      d += ml;
+    }
+    if (d != sg.out_len) throw std::runtime_error("replay: segment size mismatch");
+  }
+  for (const auto* lits : {&R.lits_lane, &R.lits_wave})
+    for (const DevLit& L : *lits)
+      std::memcpy(dec + L.b, raw + (L.a & ((1ull << 40) - 1)), L.a >> 40);
+  for (const DevBrInl& r : R.brinl) {
+    uint8_t* o = dec + (r.meta & ((1ull << 40) - 1));
+    uint32_t len = (uint32_t)(r.meta >> 40) & 0xfff;
+    uint32_t period = (uint32_t)(r.meta >> 52);
+    for (uint32_t j = 0; j < len; j++)
+      o[j] = (uint8_t)(r.pat >> ((j % period) * 8));
+  }
+  for (const auto* recs : {&R.res_lane, &R.res_wave})
+    for (const DevBrRes& rec : *recs) {
+      uint32_t pat_off = 0;
+      for (uint32_t k = 0; k < rec.piece_n; k++) {
+        const DevPiece& pc = R.piece_pool[rec.piece_start + k];
+        for (uint32_t base = pat_off; base < rec.len; base += rec.off) {
+          uint32_t m = std::min(pc.len, rec.len - base);
+          for (uint32_t j = 0; j < m; j++)
+            dec[rec.dst + base + j] = dec[pc.src + j];
+        }
+        pat_off += pc.len;
+      }
+    }
+  for (const DevPageBr& pb : R.pagebrs)
+    for (uint32_t r = 0; r < pb.count; r++) {
+      const DevBr& br = R.brs[pb.start + r];
+      for (uint32_t i = 0; i < br.len; i++) dec[br.dst + i] = dec[br.src + i];
+    }
+}
+
+// every record must stay inside the raw buffer / the image part of the
+// arena before anything is launched
+void check_decomp_bounds(const DecompRecs& R, uint64_t raw_len,
+                         uint64_t img_len) {
+  auto need = [](bool ok) {
+    if (!ok) throw std::runtime_error("decompress record out of bounds");
+  };
+  for (const DevSeg& s : R.segs)
+    need(s.src_off + s.comp_len <= raw_len && s.dst_off + s.out_len <= img_len);
+  for (const auto* lits : {&R.lits_lane, &R.lits_wave})
+    for (const DevLit& L : *lits)
+      need((L.a & ((1ull << 40) - 1)) + (L.a >> 40) <= raw_len &&
+           L.b + (L.a >> 40) <= img_len);
+  for (const DevBrInl& r : R.brinl) {
+    uint64_t period = r.meta >> 52;
+    need(period >= 1 && period <= 8 &&
+         (r.meta & ((1ull << 40) - 1)) + ((r.meta >> 40) & 0xfff) <= img_len);
+  }
+  for (const auto* recs : {&R.res_lane, &R.res_wave})
+    for (const DevBrRes& r : *recs) {
+      need(r.off >= 1 && r.dst + r.len <= img_len &&
+           (uint64_t)r.piece_start + r.piece_n <= R.piece_pool.size());
+      for (uint32_t k = 0; k < r.piece_n; k++) {
+        const DevPiece& pc = R.piece_pool[r.piece_start + k];
+        need(pc.src + pc.len <= img_len);
+      }
+    }
+  for (const DevPageBr& pb : R.pagebrs) {
+    need((uint64_t)pb.start + pb.count <= R.brs.size());
+    for (uint32_t r = 0; r < pb.count; r++) {
+      const DevBr& br = R.brs[pb.start + r];
+      need(br.src < br.dst && br.dst + br.len <= img_len);
+    }
+  }
+  for (const auto& h : R.himgs) need(h.first + h.second.size() <= img_len);
+}
+
+struct DevBufs {
+  std::vector<void*> ptrs;
+  hipStream_t stream = nullptr;
+  template <class T> T* alloc(size_t bytes) {
+    void* p = nullptr;
+    HIP_TRY(hipMalloc(&p, std::max<size_t>(bytes, 16)));
+    ptrs.push_back(p);
+    return (T*)p;
+  }
+  template <class T> T* upload(const std::vector<T>& v) {
+    T* d = alloc<T>(v.size() * sizeof(T));
+    if (!v.empty())
+      HIP_TRY(hipMemcpyAsync(d, v.data(), v.size() * sizeof(T),
+                             hipMemcpyHostToDevice, stream));
+    return d;
+  }
+  ~DevBufs() {
+    for (void* p : ptrs) (void)hipFree(p);
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+};
+
+}  // namespace
+
+extern "C" int32_t gpuq_test_decompress(
+    gpuq_ctx* ctx, const gpuq_decomp_page* pages, int32_t n_pages,
+    int32_t raw_lead, int32_t mode, uint8_t sentinel, uint8_t* out,
+    uint64_t out_cap, uint64_t* arena_len, uint64_t* guard_len,
+    gpuq_decomp_stats* stats, int32_t* d_err) try {
+  const int pmode = mode & 0xff;
+  const bool host_only = mode & (GPUQ_DECOMP_HOST_ONLY | GPUQ_DECOMP_HOST_REPLAY);
+  const bool replay = mode & GPUQ_DECOMP_HOST_REPLAY;
+  if (!pages || n_pages < 0 || raw_lead < 0 || raw_lead > 15 || !out ||
+      !stats || pmode > GPUQ_DECOMP_FORCE_FALLBACK ||
+      (mode & ~(0xff | GPUQ_DECOMP_HOST_ONLY | GPUQ_DECOMP_HOST_REPLAY)))
+    throw std::runtime_error("gpuq_test_decompress: bad argument");
+  if (!host_only && (!ctx || ctx->devices.empty()))
+    throw std::runtime_error("gpuq_test_decompress: device mode needs a session");
+
+  // layout: blocks packed after raw_lead; images 16-aligned, pad after
+  std::vector<uint64_t> src_off(n_pages), dst_off(n_pages);
+  uint64_t raw_len = (uint64_t)raw_lead, img_len = 0;
+  for (int32_t i = 0; i < n_pages; i++) {
+    const int codec = pages[i].codec;
+    if (codec != CODEC_UNCOMPRESSED && codec != CODEC_SNAPPY &&
+        codec != CODEC_LZ4_RAW)
+      throw std::runtime_error("gpuq_test_decompress: unsupported codec");
+    if (codec == CODEC_UNCOMPRESSED && pages[i].comp_len != pages[i].uncomp_len)
+      throw std::runtime_error("gpuq_test_decompress: uncompressed size mismatch");
+    src_off[i] = raw_len;
+    dst_off[i] = img_len;
+    raw_len += pages[i].comp_len;
+    img_len += ((uint64_t)pages[i].uncomp_len + 15) & ~15ull;
+  }
+  const uint64_t arena = img_len + DEC_PAD;
+  if (arena_len) *arena_len = arena;
+  if (guard_len) *guard_len = DEC_PAD;
+  if (d_err) *d_err = 0;
+  if (out_cap < arena)
+    throw std::runtime_error("gpuq_test_decompress: output buffer too small");
+
+  // plan every page first: a stream the walk rejects throws here, before
+  // anything is allocated or enqueued
+  DecompRecs R;
+  for (int32_t i = 0; i < n_pages; i++)
+    plan_decomp_page(R, pages[i].codec, pages[i].comp, src_off[i], dst_off[i],
+                     pages[i].comp_len, pages[i].uncomp_len,
+                     pages[i].codec == CODEC_UNCOMPRESSED, pmode, &stats[i]);
+  check_decomp_bounds(R, raw_len, img_len);
+
+  std::vector<uint8_t> raw;
+  if (!host_only || replay) {
+    raw.assign(raw_len + (replay ? RAW_SLACK : 0), 0);
+    for (int32_t i = 0; i < n_pages; i++)
+      if (pages[i].comp_len)
+        std::memcpy(raw.data() + src_off[i], pages[i].comp, pages[i].comp_len);
+  }
+
+  if (host_only) {
+    std::memset(out, sentinel, arena);
+    if (replay) {
+      replay_decompress(raw.data(), out, R);
+      for (const auto& h : R.himgs)
+        std::memcpy(out + h.first, h.second.data(), h.second.size());
+      return 0;
+    }
+    for (int32_t i = 0; i < n_pages; i++) {
+      const gpuq_decomp_page& p = pages[i];
+      uint8_t* o = out + dst_off[i];
+      int got;
+      if (stats[i].mode == GPUQ_DECOMP_PAGE_RAW) {
+        if (p.uncomp_len) std::memcpy(o, p.comp, p.uncomp_len);
+        got = (int)p.uncomp_len;
+      } else if (p.codec == CODEC_SNAPPY) {
+        got = snappy_decompress_host(p.comp, p.comp_len, o, p.uncomp_len);
+      } else {
+        got = lz4_decompress_host(p.comp, p.comp_len, o, p.uncomp_len);
+      }
+      if (got != (int)p.uncomp_len)
+        throw std::runtime_error("gpuq_test_decompress: host decode failure");
+    }
+    return 0;
+  }
+
+  HIP_TRY(hipSetDevice(ctx->devices[0]));
+  DevBufs B;
+  HIP_TRY(hipStreamCreateWithFlags(&B.stream, hipStreamNonBlocking));
+  uint8_t* d_raw = B.alloc<uint8_t>(raw_len + RAW_SLACK);
+  uint8_t* d_dec = B.alloc<uint8_t>(arena);
+  int32_t* d_e = B.alloc<int32_t>(4);
+  HIP_TRY(hipMemsetAsync(d_dec, sentinel, arena, B.stream));
+  HIP_TRY(hipMemsetAsync(d_e, 0, 4, B.stream));
+  if (raw_len)
+    HIP_TRY(hipMemcpyAsync(d_raw, raw.data(), raw_len, hipMemcpyHostToDevice,
+                           B.stream));
+  for (const auto& h : R.himgs)
+    if (!h.second.empty())
+      HIP_TRY(hipMemcpyAsync(d_dec + h.first, h.second.data(), h.second.size(),
+                             hipMemcpyHostToDevice, B.stream));
+  DecompDev D{
+      d_raw, d_dec,
+      B.upload(R.segs), (int)R.segs.size(),
+      B.upload(R.lits_lane), (int64_t)R.lits_lane.size(),
+      B.upload(R.lits_wave), (int)R.lits_wave.size(),
+      B.upload(R.brinl), (int64_t)R.brinl.size(),
+      B.upload(R.res_lane), (int64_t)R.res_lane.size(),
+      B.upload(R.res_wave), (int)R.res_wave.size(),
+      B.upload(R.piece_pool), B.upload(R.brs),
+      B.upload(R.pagebrs), (int)R.pagebrs.size(), d_e};
+  launch_decompress(B.stream, D);
+  HIP_TRY(hipGetLastError());
+  int32_t err = 0;
+  HIP_TRY(hipMemcpyAsync(out, d_dec, arena, hipMemcpyDeviceToHost, B.stream));
+  HIP_TRY(hipMemcpyAsync(&err, d_e, 4, hipMemcpyDeviceToHost, B.stream));
+  HIP_TRY(hipStreamSynchronize(B.stream));
+  if (d_err) *d_err = err;
+  return 0;
+} catch (const std::exception& e) {
+  if (ctx) ctx->set_error(e.what());
+  else g_null_ctx_error = e.what();
+  return -1;
+}

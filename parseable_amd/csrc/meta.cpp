@@ -291,7 +291,7 @@ int snappy_decompress_host(const uint8_t* src, size_t comp, uint8_t* dst,
   uint64_t ulen = 0;
   int sh = 0;
   for (;;) {
-    if (s >= comp) return -1;
+    if (s >= comp || sh > 63) return -1;  // a uvarint64 has <= 10 bytes
     uint8_t b = src[s++];
     ulen |= (uint64_t)(b & 0x7f) << sh;
     if (!(b & 0x80)) break;
@@ -422,6 +422,8 @@ Lz4Plan snappy_walk(const uint8_t* src, size_t comp, size_t uncomp) {
   int sh = 0;
   for (;;) {
     if (s >= comp) throw std::runtime_error("snappy walk: eof in preamble");
+    if (sh > 63)  // a uvarint64 has <= 10 bytes; a larger shift is undefined
+      throw std::runtime_error("snappy walk: preamble too long");
     uint8_t b = src[s++];
     ulen |= (uint64_t)(b & 0x7f) << sh;
     if (!(b & 0x80)) break;
