@@ -135,7 +135,25 @@ typedef struct {
 
 typedef enum {
   GPUQ_AGG_COUNT_STAR = 0, GPUQ_AGG_COUNT, GPUQ_AGG_SUM,
-  GPUQ_AGG_MIN, GPUQ_AGG_MAX
+  GPUQ_AGG_MIN, GPUQ_AGG_MAX,
+  /* COUNT(DISTINCT column) (AggregateFunction::CountDistinct,
+   * alerts/alert_enums.rs:300, alerts/mod.rs:341-346): the number of
+   * distinct non-NULL values of `column` among the selected rows of the
+   * group.
+   *  - NULLs are ignored; a group (or the no-group row) with no non-NULL
+   *    selected value gives 0 — the result is never NULL;
+   *  - utf8 compares by bytes; i64 / i32 / timestamp by value; f64 under the
+   *    normalisation of f64 group keys (-0.0 folds into +0.0, every NaN into
+   *    one canonical NaN — a possible difference from an engine that
+   *    compares raw bits);
+   *  - column == NULL or a missing column is a plan-build error; the agg is
+   *    not allowed together with a projection; a bare count_distinct never
+   *    takes the manifest count fast path;
+   *  - it does not merge by + / min / max: the partial batch carries, after
+   *    all fixed columns, one `agg{i}_set` list column per distinct agg with
+   *    the group's distinct values, and the Final merge unions them (see
+   *    gpuq_plan_execute). */
+  GPUQ_AGG_COUNT_DISTINCT
 } gpuq_agg_op;
 
 typedef struct { int32_t op; const char* column; } gpuq_agg;
@@ -201,7 +219,14 @@ int32_t gpuq_plan_load(gpuq_plan*, int32_t partition);
  * projected rows) as one Arrow record batch through `out`. The caller
  * merges partials across partitions/nodes — the AggregateExec
  * Partial->Final split of the reference's engine.
- * Replaces ExecutionPlan::execute(partition, ctx) -> RecordBatch stream. */
+ * Replaces ExecutionPlan::execute(partition, ctx) -> RecordBatch stream.
+ * Partial layout: keys..., __presence, then agg{i}, agg{i}_count per
+ * aggregate. For GPUQ_AGG_COUNT_DISTINCT both are the int64 partition-local
+ * distinct count (final when there is one partial), and after all of those
+ * columns follows, per distinct agg in agg order, agg{i}_set: a never-null
+ * list<utf8 | int64 | float64> of the group's distinct non-NULL values in
+ * unspecified order (empty for none) — DataFusion's distinct-count
+ * accumulator state is a list too. */
 int32_t gpuq_plan_execute(gpuq_plan*, int32_t partition,
                           struct ArrowArrayStream* out);
 

@@ -86,7 +86,8 @@ OPS = {"eq": 0, "ne": 1, "lt": 2, "le": 3, "gt": 4, "ge": 5, "between": 6, "cont
 STR_OPS = ("contains", "icontains", "starts_with", "ends_with", "not_contains",
            "not_icontains", "not_starts_with", "not_ends_with")
 NULL_OPS = ("is_null", "is_not_null")
-AGGS = {"count_star": 0, "count": 1, "sum": 2, "min": 3, "max": 4}
+AGGS = {"count_star": 0, "count": 1, "sum": 2, "min": 3, "max": 4,
+        "count_distinct": 5}
 
 _lib = None
 

@@ -89,7 +89,9 @@ constexpr int cmp_str_like_mode(int op) {
 enum { AGGK_COUNT_STAR = 0, AGGK_COUNT, AGGK_SUM_I64, AGGK_SUM_F64,
        AGGK_MIN_I64, AGGK_MAX_I64, AGGK_MIN_F64, AGGK_MAX_F64,
        AGGK_MIN_RANK, AGGK_MAX_RANK,   // utf8 min/max via dict sort-ranks
-       AGGK_MIN_STR, AGGK_MAX_STR };   // utf8 min/max via strrefs (hash cols)
+       AGGK_MIN_STR, AGGK_MAX_STR,     // utf8 min/max via strrefs (hash cols)
+       AGGK_COUNT_DISTINCT };          // a no-op slot for k_agg: counted by the
+                                       // distinct-set pass (DistinctArgs)
 
 constexpr int MAX_KEYS = 4;
 constexpr int MAX_AGGS = 8;
@@ -125,9 +127,30 @@ struct AggArgs {
   int32_t* err;
 };
 
+// COUNT(DISTINCT col): one pass per distinct aggregate over the final masks
+// and gids. The per-row key is (g << 32) | vgid — g the group index k_agg
+// computes from key_gid[]/key_size[] (the cascaded gid, or 0 with no keys),
+// vgid the value column's dense per-partition gid (0 = NULL, skipped). Both
+// set kernels leave an unordered list of the claimed keys plus a count.
+struct DistinctArgs {
+  const uint8_t* mask;          // selection mask, may be null (= all)
+  int64_t n_rows;
+  int n_keys;
+  const int32_t* key_gid[MAX_KEYS];
+  int32_t key_size[MAX_KEYS];
+  int32_t n_groups;             // bound on g (checked, ERR_DICT_RANGE)
+  const int32_t* vgid;
+  int32_t vcard;                // bound on vgid: cardinality incl. null slot
+  uint64_t* pairs;              // out: claimed keys
+  uint32_t* count;              // out: number of claimed keys
+  uint32_t pair_cap;            // capacity of `pairs` (ERR_DISTINCT_CAP)
+  int32_t* err;
+};
+
 // error codes written to *d_error by kernels
 enum { ERR_NONE = 0, ERR_LZ4 = 1, ERR_RLE = 2, ERR_DELTA = 3, ERR_DICT_RANGE = 4,
        ERR_PAGE = 5, ERR_FSUM_RANGE = 6, ERR_HASH_CAP = 7, ERR_HASH_PROBE = 8,
-       ERR_PAIR_CAP = 9, ERR_PAIR_PROBE = 10 };
+       ERR_PAIR_CAP = 9, ERR_PAIR_PROBE = 10, ERR_DISTINCT_CAP = 11,
+       ERR_DISTINCT_PROBE = 12 };
 
 }  // namespace gpuq

@@ -174,6 +174,10 @@ struct ColPlan {
   // (k_numhash_*); d_val carries the key values, d_gid the assigned gids
   bool numeric_key = false;
   bool need_gid_valid = false;  // validity bytes alongside gid (COUNT(utf8))
+  // COUNT(DISTINCT col): decoded exactly as a hidden group key (need_gid /
+  // hash_mode / numeric_key give a dense per-partition gid, 0 = NULL) but
+  // never part of group_cols, n_groups or the cascade
+  bool distinct_val = false;
   // predicate routing
   std::vector<int> lut_preds;      // preds evaluated per-dict-entry (utf8)
   std::vector<int> cmp_preds;      // preds on the decoded i64 array
@@ -346,6 +350,11 @@ struct Partition {
   // column's dict and PLAIN page ids merged in page order
   std::vector<int32_t> valagg_ids;
   int32_t* d_valagg_ids = nullptr;
+  // COUNT(DISTINCT): the bitmap (distinct_bitmap_bits, shared by the
+  // passes), and per distinct agg the claimed-key list and its counter
+  uint64_t* d_dbitmap = nullptr;
+  std::vector<uint64_t*> d_dpairs;
+  uint32_t* d_dcount = nullptr;
   int64_t load_ns = 0;
 };
 
@@ -375,6 +384,13 @@ struct Ring {
 namespace {
 constexpr int HASH_LOG2 = 24;          // shared open-addressing table slots
 constexpr int32_t GID_CAP = 1 << 22;   // max distinct groups (per col & total)
+// COUNT(DISTINCT): claimed (group, value) pairs per partition — load factor
+// 0.5 of the shared table — and the bitmap path's default size (32 MB)
+constexpr uint32_t DISTINCT_PAIR_CAP = 1u << 23;
+constexpr uint64_t DISTINCT_BITMAP_BITS = 1ull << 28;
+// bitmaps up to this size are marked through a block-local LDS copy (16 KiB:
+// small enough to keep the CU full of blocks); at most 64 KiB of LDS
+constexpr uint64_t DISTINCT_LDS_BITS = 1ull << 17;
 }  // namespace
 
 struct gpuq_plan {
@@ -406,6 +422,16 @@ struct gpuq_plan {
                                  // numeric key): the old kernels stay armed
   int valagg_blocks = 1024;      // persistent grid cap
   bool exec_dbg = false;         // GPUQ_PLAN_DEBUG at build: log the agg path
+  // COUNT(DISTINCT) (read at plan build): aggs of that kind in agg order;
+  // bitmap path when n_groups x padded value cardinality fits
+  // distinct_bitmap_bits (GPUQ_DISTINCT_BITMAP_BITS) and
+  // GPUQ_DISTINCT_FORCE_HASH is unset; the claimed-pair list holds
+  // distinct_pair_cap keys (GPUQ_DISTINCT_PAIR_CAP lowers it)
+  std::vector<int> distinct_aggs;
+  uint64_t distinct_bitmap_bits = DISTINCT_BITMAP_BITS;
+  uint64_t distinct_lds_bits = DISTINCT_LDS_BITS;  // GPUQ_DISTINCT_LDS_BITS
+  uint32_t distinct_pair_cap = DISTINCT_PAIR_CAP;
+  bool distinct_force_hash = false;
   std::mutex mu;
   // metrics
   int64_t m_rows_scanned = 0, m_rows_out = 0, m_kernel_ns = 0, m_exec_ns = 0,
@@ -1065,6 +1091,13 @@ extern "C" gpuq_plan* gpuq_plan_build(
   for (int32_t i = 0; i < n_aggs; i++) {
     AggPlan ap;
     ap.op = aggs[i].op;
+    if (aggs[i].op == GPUQ_AGG_COUNT_DISTINCT) {
+      if (!aggs[i].column)
+        throw std::runtime_error("count_distinct needs a column");
+      if (n_projection > 0)
+        throw std::runtime_error(
+            "count_distinct is not allowed in a projection plan");
+    }
     if (aggs[i].op != GPUQ_AGG_COUNT_STAR) {
       ap.col = aggs[i].column;
       ap.col_idx = find_or_add_col(plan->cols, ap.col);
@@ -1151,6 +1184,28 @@ extern "C" gpuq_plan* gpuq_plan_build(
     if (ap.op == GPUQ_AGG_COUNT_STAR) { ap.kind = AGGK_COUNT_STAR; continue; }
     auto& c = plan->cols[ap.col_idx];
     ap.is_f64 = (c.phys == PT_DOUBLE || c.phys == PT_FLOAT);
+    if (ap.op == GPUQ_AGG_COUNT_DISTINCT) {
+      // the value column gets a dense gid per row the way a group key does:
+      // dict utf8 via the global dictionary (hash mode is decided below,
+      // with the keys), numeric via the value hash
+      ap.kind = AGGK_COUNT_DISTINCT;
+      c.distinct_val = true;
+      if (c.phys == PT_BYTE_ARRAY) {
+        c.need_gid = true;
+      } else if (c.phys == PT_INT64 || c.phys == PT_INT32 ||
+                 c.phys == PT_DOUBLE) {
+        c.numeric_key = true;
+        c.need_val = true;
+        c.val_always = true;
+        plan->has_numkey = true;
+      } else {
+        throw std::runtime_error(
+            "unsupported count_distinct column type "
+            "(utf8/i64/i32/f64/timestamp): " + ap.col);
+      }
+      plan->distinct_aggs.push_back((int)(&ap - plan->aggs.data()));
+      continue;
+    }
     if (c.phys == PT_BYTE_ARRAY && ap.op == GPUQ_AGG_SUM)
       throw std::runtime_error("sum over utf8 column: " + ap.col);
     if (c.phys == PT_BYTE_ARRAY) {
@@ -1323,7 +1378,7 @@ extern "C" gpuq_plan* gpuq_plan_build(
             if (ap.kind == AGGK_MAX_RANK) ap.kind = AGGK_MAX_STR;
           }
       }
-      bool is_key = false;
+      bool is_key = c.distinct_val;  // gids from the hash build, like a key
       for (int gci : plan->group_cols) is_key |= (gci == (int)ci);
       if (!is_key) { c.need_gid = false; c.need_gid_valid = false; }
     }
@@ -2057,7 +2112,24 @@ extern "C" gpuq_plan* gpuq_plan_build(
   plan->exec_dbg = getenv("GPUQ_PLAN_DEBUG") != nullptr;
   if (const char* e = getenv("GPUQ_VALAGG_BLOCKS"))
     plan->valagg_blocks = std::max(1, atoi(e));
+  // COUNT(DISTINCT) knobs. The bitmap stays below 2^31 bits so the emit
+  // pass's u32 list cursor cannot wrap; the pair cap can only be lowered.
+  if (const char* e = getenv("GPUQ_DISTINCT_BITMAP_BITS"))
+    plan->distinct_bitmap_bits =
+        std::min<uint64_t>(strtoull(e, nullptr, 10), 1ull << 31);
+  if (const char* e = getenv("GPUQ_DISTINCT_LDS_BITS"))
+    plan->distinct_lds_bits =
+        std::min<uint64_t>(strtoull(e, nullptr, 10), 64 * 1024 * 8);
+  if (const char* e = getenv("GPUQ_DISTINCT_PAIR_CAP"))
+    plan->distinct_pair_cap = (uint32_t)std::min<uint64_t>(
+        std::max<uint64_t>(strtoull(e, nullptr, 10), 1), DISTINCT_PAIR_CAP);
+  if (const char* e = getenv("GPUQ_DISTINCT_FORCE_HASH"))
+    plan->distinct_force_hash = atoi(e) != 0;
+  // a distinct agg keeps the plan off both fused paths (their shapes admit
+  // no third kind of aggregate; stated here so a later shape cannot let one in)
+  if (!plan->distinct_aggs.empty()) plan->fused_count = false;
   if (!plan->is_projection && !getenv("GPUQ_NO_FUSED_VALAGG") &&
+      plan->distinct_aggs.empty() &&
       plan->group_cols.size() == 1 && plan->aggs.size() == 2 &&
       plan->aggs[0].kind == AGGK_COUNT_STAR && plan->n_fsum == 0 &&
       (plan->aggs[1].kind == AGGK_SUM_I64 || plan->aggs[1].kind == AGGK_MIN_I64 ||
@@ -2103,6 +2175,12 @@ extern "C" gpuq_plan* gpuq_plan_build(
             (int)plan->fused_count, (int)plan->fused_valagg,
             plan->fused_valagg && plan->valagg_late
                 ? " (group count checked at execute)" : "");
+    for (int ai : plan->distinct_aggs) {
+      const auto& c = plan->cols[plan->aggs[ai].col_idx];
+      fprintf(stderr, "[gpuq plan] distinct agg=%d col=%s gids=%s\n", ai,
+              c.name.c_str(),
+              c.numeric_key ? "numeric" : c.hash_mode ? "hash" : "dict");
+    }
     for (size_t p = 0; p < plan->parts.size(); p++) {
       const auto& pt = plan->parts[p];
       fprintf(stderr,
@@ -2351,6 +2429,29 @@ extern "C" int32_t gpuq_plan_load(gpuq_plan* plan, int32_t pi) try {
       for (auto& ptr : part.d_gid2pair)
         HIP_TRY(hipMalloc(&ptr, (size_t)GID_CAP * 8));
     }
+  }
+  if (!plan->distinct_aggs.empty()) {
+    // the hash-set path claims in the shared table (any cardinality can
+    // fall to it); hash / numeric value columns resolve gids through a
+    // gid2ref map of their own, like keys
+    if (!part.d_hkeys)
+      HIP_TRY(hipMalloc(&part.d_hkeys, ((1ull << HASH_LOG2) + 1) * 8));
+    for (int ai : plan->distinct_aggs) {
+      int ci = plan->aggs[ai].col_idx;
+      const auto& c = plan->cols[ci];
+      if ((c.hash_mode || c.numeric_key) && !part.d_gid2ref.count(ci)) {
+        uint64_t* g2r = nullptr;
+        HIP_TRY(hipMalloc(&g2r, (size_t)GID_CAP * 8));
+        part.d_gid2ref[ci] = g2r;
+      }
+      uint64_t* pl = nullptr;
+      HIP_TRY(hipMalloc(&pl, (size_t)plan->distinct_pair_cap * 8));
+      part.d_dpairs.push_back(pl);
+    }
+    HIP_TRY(hipMalloc(&part.d_dcount, plan->distinct_aggs.size() * 4));
+    if (!plan->distinct_force_hash)
+      HIP_TRY(hipMalloc(&part.d_dbitmap,
+                        std::max<uint64_t>(plan->distinct_bitmap_bits / 8 + 8, 16)));
   }
   std::vector<int32_t> kinds;
   for (auto& a : plan->aggs) kinds.push_back(a.kind);
@@ -2879,6 +2980,9 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
   int64_t n_groups_exec = plan->n_groups;
   bool cascaded = false;
   std::vector<uint32_t> level_claimed;
+  // per distinct agg: 0 = the hash-set path ran, 1 = the bitmap path marking
+  // in global memory, 2 = the bitmap path marking through LDS
+  std::vector<char> distinct_bitmap(plan->distinct_aggs.size(), 0);
   auto key_card = [&](int ci) -> int64_t {
     const auto& kc = plan->cols[ci];
     return kc.is_bin ? (int64_t)kc.nbins + 1
@@ -3068,7 +3172,14 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
   // group key (one shared table, rebuilt per column); string predicates
   // evaluate over the row strrefs
   if (plan->has_hash || plan->has_numkey) {
-    for (int ci : plan->group_cols) {
+    // group keys, then the value columns of distinct aggs that are not keys
+    std::vector<int> gid_cols = plan->group_cols;
+    for (int ai : plan->distinct_aggs) {
+      int ci = plan->aggs[ai].col_idx;
+      if (std::find(gid_cols.begin(), gid_cols.end(), ci) == gid_cols.end())
+        gid_cols.push_back(ci);
+    }
+    for (int ci : gid_cols) {
       auto& c = plan->cols[ci];
       if (!c.hash_mode && !c.numeric_key) continue;
       HIP_TRY(hipMemsetAsync(part.d_hkeys, 0xFF,
@@ -3274,6 +3385,40 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
         if (kv.first.second == plan->valagg_col) run_task(kv);
     launch_agg(st, a);
   }
+  // 3b. COUNT(DISTINCT): one set pass per distinct agg over the same final
+  // masks and group index; the shared table is free again (cascade done)
+  for (size_t di = 0; di < plan->distinct_aggs.size(); di++) {
+    const int ci = plan->aggs[plan->distinct_aggs[di]].col_idx;
+    DistinctArgs d{};
+    d.mask = a.mask;
+    d.n_rows = part.n_rows;
+    d.n_keys = a.n_keys;
+    for (int k = 0; k < a.n_keys; k++) {
+      d.key_gid[k] = a.key_gid[k];
+      d.key_size[k] = a.key_size[k];
+    }
+    d.n_groups = (int32_t)n_groups_exec;
+    d.vgid = part.d_gid[ci];
+    d.vcard = (int32_t)key_card(ci);
+    d.pairs = part.d_dpairs[di];
+    d.count = part.d_dcount + di;
+    d.pair_cap = plan->distinct_pair_cap;
+    d.err = part.d_err;
+    const uint64_t vpad = ((uint64_t)d.vcard + 63) & ~63ull;
+    const uint64_t bits = (uint64_t)n_groups_exec * vpad;
+    if (!plan->distinct_force_hash && part.d_dbitmap &&
+        bits <= plan->distinct_bitmap_bits)
+      distinct_bitmap[di] = bits <= plan->distinct_lds_bits ? 2 : 1;
+    HIP_TRY(hipMemsetAsync(d.count, 0, 4, st));
+    if (distinct_bitmap[di]) {
+      HIP_TRY(hipMemsetAsync(part.d_dbitmap, 0, bits / 8, st));
+      launch_distinct_bitmap(st, d, part.d_dbitmap, (uint32_t)vpad,
+                             distinct_bitmap[di] == 2);
+    } else {
+      HIP_TRY(hipMemsetAsync(part.d_hkeys, 0xFF, (1ull << HASH_LOG2) * 8, st));
+      launch_distinct_claim(st, d, part.d_hkeys, HASH_LOG2);
+    }
+  }
   HIP_TRY(hipEventRecord(ev1, st));
   }  // !fused_count
 
@@ -3288,9 +3433,47 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
                            hipMemcpyDeviceToHost, st));
   int32_t herr = 0;
   HIP_TRY(hipMemcpyAsync(&herr, part.d_err, 4, hipMemcpyDeviceToHost, st));
+  const size_t n_distinct = plan->distinct_aggs.size();
+  std::vector<uint32_t> dcounts(n_distinct, 0);
+  if (n_distinct)
+    HIP_TRY(hipMemcpyAsync(dcounts.data(), part.d_dcount, n_distinct * 4,
+                           hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
+  if (herr == ERR_DISTINCT_CAP)
+    throw std::runtime_error(
+        "count_distinct: more than " + std::to_string(plan->distinct_pair_cap) +
+        " distinct (group, value) pairs in one partition (the pair cap, "
+        "GPUQ_DISTINCT_PAIR_CAP) — kernel error code " + std::to_string(herr));
+  if (herr == ERR_DISTINCT_PROBE)
+    throw std::runtime_error(
+        "count_distinct: hash-set probe exhausted — kernel error code " +
+        std::to_string(herr));
   if (herr != 0)
     throw std::runtime_error("kernel error code " + std::to_string(herr));
+  // the claimed (g << 32 | vgid) lists, sorted: group order == live order
+  std::vector<std::vector<uint64_t>> dpairs(n_distinct);
+  for (size_t di = 0; di < n_distinct; di++) {
+    if (dcounts[di] > plan->distinct_pair_cap)
+      throw std::runtime_error("count_distinct: pair count beyond the cap");
+    dpairs[di].resize(dcounts[di]);
+    if (dcounts[di])
+      HIP_TRY(hipMemcpy(dpairs[di].data(), part.d_dpairs[di],
+                        (size_t)dcounts[di] * 8, hipMemcpyDeviceToHost));
+    std::sort(dpairs[di].begin(), dpairs[di].end());
+    if (plan->exec_dbg) {
+      const int ai = plan->distinct_aggs[di];
+      const int ci = plan->aggs[ai].col_idx;
+      fprintf(stderr,
+              "[gpuq exec] part %d: distinct agg=%d col=%s path=%s groups=%lld "
+              "card=%lld pairs=%u%s\n",
+              pi, ai, plan->cols[ci].name.c_str(),
+              distinct_bitmap[di] ? "bitmap" : "hash",
+              (long long)n_groups_exec, (long long)key_card(ci) - 1,
+              dcounts[di],
+              distinct_bitmap[di] == 2   ? " mark=lds"
+              : distinct_bitmap[di] == 1 ? " mark=global" : "");
+    }
+  }
   hot_tier_populate(plan, part, st);
 
   float ms_total = 0, ms_decomp = 0;
@@ -3317,7 +3500,12 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
   ss->schema.format = strdup("+s");
   ss->schema.name = strdup("");
   ss->schema.release = release_schema;
-  int n_fields = n_keys + 1 + 2 * n_aggs;
+  // fixed positional layout, then one agg{i}_set list per distinct agg
+  int n_fields = n_keys + 1 + 2 * n_aggs + (int)n_distinct;
+  auto distinct_fmt = [&](int ai) {
+    const auto& c = plan->cols[plan->aggs[ai].col_idx];
+    return c.phys == PT_BYTE_ARRAY ? "u" : c.phys == PT_DOUBLE ? "g" : "l";
+  };
   ss->schema.n_children = n_fields;
   ss->schema.children = (struct ArrowSchema**)calloc(n_fields, sizeof(void*));
   int f = 0;
@@ -3345,6 +3533,15 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
     ss->schema.children[f] = (struct ArrowSchema*)malloc(sizeof(struct ArrowSchema));
     make_schema_field(ss->schema.children[f], "l", "agg" + std::to_string(i) + "_count");
     f++;
+  }
+  for (int ai : plan->distinct_aggs) {
+    auto* ls = (struct ArrowSchema*)malloc(sizeof(struct ArrowSchema));
+    ss->schema.children[f++] = ls;
+    make_schema_field(ls, "+l", "agg" + std::to_string(ai) + "_set");
+    ls->n_children = 1;
+    ls->children = (struct ArrowSchema**)calloc(1, sizeof(void*));
+    ls->children[0] = (struct ArrowSchema*)malloc(sizeof(struct ArrowSchema));
+    make_schema_field(ls->children[0], distinct_fmt(ai), "item");
   }
 
   auto* eb = new ExportedBatch();
@@ -3529,10 +3726,41 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
   int64_t rows_out_total = 0;
   for (int64_t r = 0; r < nr; r++)
     rows_out_total += empty_aggregate_row ? 0 : (int64_t)table[(size_t)live[r] * slots];
+  // distinct aggs: row r owns the sorted pairs [doffs[r], doffs[r + 1]) —
+  // list offsets and, by difference, the partition-local distinct counts
+  std::vector<std::vector<int32_t>> doffs(n_distinct);
+  for (size_t di = 0; di < n_distinct; di++) {
+    const auto& pr = dpairs[di];
+    auto& off = doffs[di];
+    off.assign((size_t)nr + 1, 0);
+    size_t p = 0;
+    for (int64_t r = 0; r < nr; r++) {
+      off[r] = (int32_t)p;
+      while (p < pr.size() && (int64_t)(pr[p] >> 32) == live[r]) p++;
+    }
+    off[nr] = (int32_t)p;
+    if (p != pr.size())
+      throw std::runtime_error("count_distinct: pair outside the live groups");
+  }
   // aggs
   for (int i = 0; i < n_aggs; i++) {
     auto* chv = make_child(f++);
     int kind = plan->aggs[i].kind;
+    if (kind == AGGK_COUNT_DISTINCT) {
+      size_t di = std::find(plan->distinct_aggs.begin(),
+                            plan->distinct_aggs.end(), i) -
+                  plan->distinct_aggs.begin();
+      auto* chc = make_child(f++);
+      for (auto* ch : {chv, chc}) {
+        ch->n_buffers = 2;
+        ch->buffers = (const void**)calloc(2, sizeof(void*));
+        int64_t* v = (int64_t*)eb->grab(nr * 8);
+        for (int64_t r = 0; r < nr; r++)
+          v[r] = doffs[di][r + 1] - doffs[di][r];
+        ch->buffers[1] = v;
+      }
+      continue;
+    }
     bool is_rank = (kind == AGGK_MIN_RANK || kind == AGGK_MAX_RANK ||
                     kind == AGGK_MIN_STR || kind == AGGK_MAX_STR);
     uint8_t* validity = (uint8_t*)eb->grab((nr + 7) / 8);
@@ -3656,6 +3884,70 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
     }
     chc->buffers[1] = cv;
   }
+  // agg{i}_set: the partial state of a distinct agg — per row the list of
+  // its distinct values, vgid resolved through the global dictionary (dict
+  // utf8), gid2ref + the dec arena (hash-mode utf8) or gid2ref (numeric)
+  for (size_t di = 0; di < n_distinct; di++) {
+    const int ci = plan->aggs[plan->distinct_aggs[di]].col_idx;
+    const auto& c = plan->cols[ci];
+    const auto& pr = dpairs[di];
+    const int64_t np = (int64_t)pr.size();
+    auto* chl = make_child(f++);
+    chl->n_buffers = 2;
+    chl->buffers = (const void**)calloc(2, sizeof(void*));
+    int32_t* loffs = (int32_t*)eb->grab(((size_t)nr + 1) * 4);
+    memcpy(loffs, doffs[di].data(), ((size_t)nr + 1) * 4);
+    chl->buffers[1] = loffs;
+    chl->n_children = 1;
+    chl->children = (struct ArrowArray**)calloc(1, sizeof(void*));
+    auto* item = (struct ArrowArray*)calloc(1, sizeof(struct ArrowArray));
+    chl->children[0] = item;
+    item->length = np;
+    item->release = release_array;
+    std::vector<uint64_t> g2r;  // gid - 1 -> strref / value bits
+    if (c.hash_mode || c.numeric_key) {
+      g2r.resize(part.hash_claimed[ci]);
+      if (!g2r.empty())
+        HIP_TRY(hipMemcpy(g2r.data(), part.d_gid2ref[ci], g2r.size() * 8,
+                          hipMemcpyDeviceToHost));
+    }
+    auto vgid_of = [&](int64_t p) { return (size_t)(uint32_t)pr[(size_t)p]; };
+    if (c.numeric_key) {
+      item->n_buffers = 2;
+      item->buffers = (const void**)calloc(2, sizeof(void*));
+      int64_t* v = (int64_t*)eb->grab((size_t)np * 8);
+      for (int64_t p = 0; p < np; p++) v[p] = (int64_t)g2r.at(vgid_of(p) - 1);
+      item->buffers[1] = v;
+      continue;
+    }
+    std::vector<std::string> ref_strs;
+    if (c.hash_mode) {
+      std::vector<uint64_t> refs((size_t)np);
+      for (int64_t p = 0; p < np; p++) refs[(size_t)p] = g2r.at(vgid_of(p) - 1);
+      ref_strs = fetch_ref_strings(part, st, refs);
+    }
+    auto str_of = [&](int64_t p) -> const std::string& {
+      return c.hash_mode ? ref_strs[(size_t)p] : c.gdict.at(vgid_of(p) - 1);
+    };
+    size_t total = 0;
+    for (int64_t p = 0; p < np; p++) total += str_of(p).size();
+    if (total > (size_t)INT32_MAX)
+      throw std::runtime_error("count_distinct: set column beyond 2 GiB");
+    item->n_buffers = 3;
+    item->buffers = (const void**)calloc(3, sizeof(void*));
+    int32_t* soffs = (int32_t*)eb->grab(((size_t)np + 1) * 4);
+    char* sdata = (char*)eb->grab(total);
+    size_t off = 0;
+    for (int64_t p = 0; p < np; p++) {
+      soffs[p] = (int32_t)off;
+      const auto& s = str_of(p);
+      memcpy(sdata + off, s.data(), s.size());
+      off += s.size();
+    }
+    soffs[np] = (int32_t)off;
+    item->buffers[1] = soffs;
+    item->buffers[2] = sdata;
+  }
 
   memset(out, 0, sizeof(*out));
   out->get_schema = ss_get_schema;
@@ -3719,6 +4011,8 @@ gpuq_plan::~gpuq_plan() {
     F(part.d_rows_sorted); F(part.d_count); F(part.d_sort_temp);
     for (auto& kv : part.d_ids) F(kv.second);
     F(part.d_valagg_ids);
+    F(part.d_dbitmap); F(part.d_dcount);
+    for (auto* ptr : part.d_dpairs) F(ptr);
     for (auto& kv : part.d_gid) F(kv.second);
     for (auto& kv : part.d_val) F(kv.second);
     for (auto& kv : part.d_valid) F(kv.second);

@@ -1301,6 +1301,139 @@ __global__ void k_numhash_lookup(const int64_t* __restrict__ vals,
   }
 }
 
+// ------------------------------------------------------------------
+// COUNT(DISTINCT col): the set of (group, value-gid) keys among the selected
+// rows (DistinctArgs, dev_types.h). Almost every row repeats a key already
+// in the set, so both paths look before they write: the look is an
+// agent-scope relaxed load (served from L2 — a CU's L1 copy of a word that
+// another CU set would stay stale and every row would fall through to the
+// atomic), and a row issues an atomic only for a key it has not seen set.
+// A stale look costs one redundant atomic, never a wrong answer: bits are
+// only ever set, slots only ever go EMPTY -> key.
+// ------------------------------------------------------------------
+__device__ __forceinline__ uint64_t look64(const uint64_t* p) {
+  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// -> false for rows that contribute nothing (masked out / NULL value) or
+// whose gids are out of range (error word set: the row is dropped)
+__device__ __forceinline__ bool distinct_key(const DistinctArgs& d, int64_t i,
+                                             uint32_t& g, uint32_t& v) {
+  if (d.mask && !d.mask[i]) return false;
+  int32_t vg = d.vgid[i];
+  if (vg == 0) return false;
+  int64_t gg = 0;
+  for (int k = 0; k < d.n_keys; k++)
+    gg = gg * d.key_size[k] + d.key_gid[k][i];
+  if (vg < 0 || vg >= d.vcard || gg < 0 || gg >= d.n_groups) {
+    atomicExch(d.err, ERR_DICT_RANGE);
+    return false;
+  }
+  g = (uint32_t)gg;
+  v = (uint32_t)vg;
+  return true;
+}
+
+// bitmap path, pass 1: bit (g * vpad + v). vpad is a multiple of 64, so no
+// word spans two groups. Steady state is read-only. A small bitmap packs the
+// hot keys into a few cache lines that every CU would look at in L2 for every
+// row (measured slower than the hash set): USE_LDS keeps a
+// block-local copy in LDS — the same look-then-OR there — and merges its
+// non-zero words into the global bitmap once per block.
+template <bool USE_LDS>
+__global__ void __launch_bounds__(256)
+k_distinct_mark(DistinctArgs d, uint64_t* bitmap, uint32_t vpad,
+                int64_t n_words) {
+  extern __shared__ uint64_t lbm[];
+  if (USE_LDS) {
+    for (int64_t w = threadIdx.x; w < n_words; w += blockDim.x) lbm[w] = 0;
+    __syncthreads();
+  }
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < d.n_rows; i += stride) {
+    uint32_t g, v;
+    if (!distinct_key(d, i, g, v)) continue;
+    uint64_t bit = (uint64_t)g * vpad + v;
+    uint64_t m = 1ull << (bit & 63);
+    if (USE_LDS) {
+      uint64_t* w = lbm + (bit >> 6);
+      if (!(*(volatile uint64_t*)w & m))
+        atomicOr((unsigned long long*)w, (unsigned long long)m);
+    } else {
+      uint64_t* w = bitmap + (bit >> 6);
+      if (!(look64(w) & m))
+        atomicOr((unsigned long long*)w, (unsigned long long)m);
+    }
+  }
+  if (USE_LDS) {
+    __syncthreads();
+    for (int64_t w = threadIdx.x; w < n_words; w += blockDim.x) {
+      uint64_t m = lbm[w];
+      if (m && (look64(bitmap + w) & m) != m)
+        atomicOr((unsigned long long*)(bitmap + w), (unsigned long long)m);
+    }
+  }
+}
+// bitmap path, pass 2: one list reservation per non-zero word
+__global__ void __launch_bounds__(256)
+k_distinct_emit(const uint64_t* __restrict__ bitmap, int64_t n_words,
+                uint32_t words_per_group, uint64_t* __restrict__ pairs,
+                uint32_t* count, uint32_t pair_cap, int32_t* d_error) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (; i < n_words; i += stride) {
+    uint64_t w = bitmap[i];
+    if (!w) continue;
+    uint32_t n = (uint32_t)__popcll(w);
+    uint32_t at = atomicAdd(count, n);
+    if (at > pair_cap || n > pair_cap - at) {
+      atomicExch(d_error, ERR_DISTINCT_CAP);
+      continue;
+    }
+    const uint64_t g = (uint64_t)(i / words_per_group);
+    const uint32_t v0 = (uint32_t)(i % words_per_group) * 64;
+    while (w) {
+      int b = __ffsll((unsigned long long)w) - 1;
+      w &= w - 1;
+      pairs[at++] = (g << 32) | (v0 + (uint32_t)b);
+    }
+  }
+}
+// hash-set path: open addressing in the shared table (free once the cascade
+// lookups are done). Look first: slot == key -> done; EMPTY -> CAS; anything
+// else -> probe on. A claimer draws a list index and stores the key; nothing
+// reads a gid back, so there is no second pass and nothing to spin on.
+__global__ void __launch_bounds__(256)
+k_distinct_claim(DistinctArgs d, uint64_t* hkeys, int clog2) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const uint64_t mask = (1ull << clog2) - 1;
+  for (; i < d.n_rows; i += stride) {
+    uint32_t g, v;
+    if (!distinct_key(d, i, g, v)) continue;
+    // never HREF_EMPTY: g < 2^31
+    const uint64_t key = ((uint64_t)g << 32) | v;
+    uint64_t slot = mix64(key) & mask;
+    for (uint32_t probe = 0;; probe++) {
+      if (probe > (1u << clog2)) { atomicExch(d.err, ERR_DISTINCT_PROBE); return; }
+      uint64_t cur = look64(&hkeys[slot]);
+      if (cur == key) break;
+      if (cur == HREF_EMPTY) {
+        cur = atomicCAS((unsigned long long*)&hkeys[slot],
+                        (unsigned long long)HREF_EMPTY, (unsigned long long)key);
+        if (cur == HREF_EMPTY) {
+          uint32_t at = atomicAdd(d.count, 1u);
+          if (at >= d.pair_cap) { atomicExch(d.err, ERR_DISTINCT_CAP); return; }
+          d.pairs[at] = key;
+          break;
+        }
+        if (cur == key) break;
+      }
+      slot = (slot + 1) & mask;
+    }
+  }
+}
+
 // ASCII case fold: 'A'-'Z' -> 'a'-'z', every other byte (>= 0x80 included)
 // unchanged. fold4 is the SWAR form over four bytes: per byte, bit 7 of
 // (t + 0x3f) is set for t >= 'A' and bit 7 of (t + 0x25) for t > 'Z' (t is
@@ -2129,7 +2262,7 @@ k_agg(AggArgs a) {
       atomicAdd((unsigned long long*)&row[0], 1ull);
       for (int ai = 0; ai < a.n_aggs; ai++) {
         int k = a.agg_kind[ai];
-        if (k == AGGK_COUNT_STAR) continue;
+        if (k == AGGK_COUNT_STAR || k == AGGK_COUNT_DISTINCT) continue;
         if (a.agg_valid[ai] && !a.agg_valid[ai][i]) continue;
         if (k == AGGK_COUNT) {
           if (!a.cnt_skip[ai])
@@ -2178,6 +2311,7 @@ k_agg(AggArgs a) {
     for (int ai = 0; ai < a.n_aggs; ai++) {
       int k = a.agg_kind[ai];
       if (k == AGGK_COUNT_STAR) continue;  // == presence (export reads slot 0)
+      if (k == AGGK_COUNT_DISTINCT) continue;  // the distinct-set pass counts it
       if (a.agg_valid[ai] && !a.agg_valid[ai][i]) continue;
       if (k == AGGK_COUNT) {  // validity only; no value array needed
         if (!a.cnt_skip[ai])
@@ -2791,6 +2925,37 @@ void launch_numhash_build(hipStream_t st, const int64_t* vals,
   hipLaunchKernelGGL(k_numhash_build, dim3(blocks), dim3(256), 0, st, vals,
                      valid, n_rows, hkeys, hgids, clog2, counter, gid2key,
                      gid_cap, is_f64, d_err);
+}
+void launch_distinct_bitmap(hipStream_t st, const DistinctArgs& d,
+                            uint64_t* bitmap, uint32_t vpad, bool use_lds) {
+  const int64_t n_words = (int64_t)d.n_groups * (vpad / 64);
+  if (d.n_rows) {
+    int blocks = (int)((d.n_rows + 255) / 256);
+    if (use_lds) {
+      // fewer, longer-lived blocks: each one merges its copy once
+      if (blocks > 2048) blocks = 2048;
+      hipLaunchKernelGGL(k_distinct_mark<true>, dim3(blocks), dim3(256),
+                         (size_t)n_words * 8, st, d, bitmap, vpad, n_words);
+    } else {
+      if (blocks > 8192) blocks = 8192;
+      hipLaunchKernelGGL(k_distinct_mark<false>, dim3(blocks), dim3(256), 0,
+                         st, d, bitmap, vpad, n_words);
+    }
+  }
+  if (n_words) {
+    int blocks = (int)((n_words + 255) / 256);
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(k_distinct_emit, dim3(blocks), dim3(256), 0, st, bitmap,
+                       n_words, vpad / 64, d.pairs, d.count, d.pair_cap, d.err);
+  }
+}
+void launch_distinct_claim(hipStream_t st, const DistinctArgs& d,
+                           uint64_t* hkeys, int clog2) {
+  if (!d.n_rows) return;
+  int blocks = (int)((d.n_rows + 255) / 256);
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(k_distinct_claim, dim3(blocks), dim3(256), 0, st, d,
+                     hkeys, clog2);
 }
 void launch_numhash_lookup(hipStream_t st, const int64_t* vals,
                            const uint8_t* valid, int64_t n_rows,

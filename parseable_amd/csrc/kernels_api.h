@@ -106,6 +106,15 @@ void launch_numhash_lookup(hipStream_t, const int64_t* vals,
                            const uint8_t* valid, int64_t n_rows,
                            const uint64_t* hkeys, const int32_t* hgids,
                            int clog2, int is_f64, int32_t* out_gid);
+// COUNT(DISTINCT): both leave d.pairs / d.count filled (count zeroed by the
+// caller). bitmap: n_groups * vpad zeroed bits, vpad a multiple of 64
+// (k_distinct_mark + k_distinct_emit; use_lds: mark through a block-local LDS
+// copy of the bitmap, which must fit 64 KiB). claim: hkeys filled with 0xFF
+// (k_distinct_claim).
+void launch_distinct_bitmap(hipStream_t, const DistinctArgs& d,
+                            uint64_t* bitmap, uint32_t vpad, bool use_lds);
+void launch_distinct_claim(hipStream_t, const DistinctArgs& d, uint64_t* hkeys,
+                           int clog2);
 void launch_cmp_str(hipStream_t, const uint8_t* dec, const int64_t* refs,
                     const uint8_t* valid, const uint8_t* lit, uint32_t lit_len,
                     int op, uint8_t* mask, int64_t n_rows);

@@ -27,7 +27,8 @@ def _batch_rows(batch, n_keys, n_aggs):
         return out
     from .provider import _col_list
 
-    cols = [_col_list(batch.column(i)) for i in range(batch.num_columns)]
+    # the fixed columns only: agg{i}_set lists (count_distinct) follow them
+    cols = [_col_list(batch.column(i)) for i in range(n_keys + 1 + 2 * n_aggs)]
     for r in range(batch.num_rows):
         key = tuple(cols[k][r] for k in range(n_keys))
         presence = cols[n_keys][r]
@@ -105,6 +106,12 @@ class DistMerger:
         for i, a in enumerate(self.aggs):
             if a["agg"] in ("min", "max") and self.is_str[i]:
                 str_minmax[i] = {}
+        # count_distinct: the partial state is a set per group (the batch's
+        # agg{i}_set lists) — unioned through the same object gather. Which
+        # aggs take it follows from the query alone, so a rank with no rows
+        # agrees without any type exchange at setup.
+        dsets: list[dict | None] = [
+            {} if a["agg"] == "count_distinct" else None for a in self.aggs]
 
         np_presence = np.zeros(G, dtype=np.int64)
         np_counts = np.zeros((G, n_aggs), dtype=np.int64)
@@ -128,7 +135,15 @@ class DistMerger:
                 raise RuntimeError(f"key {e} not in agreed key space")
             np.add.at(np_presence, gis,
                       batch.column(nk).to_numpy(zero_copy_only=False).astype(np.int64))
+            from .provider import _set_member, batch_distinct_sets
+
+            set_lists = batch_distinct_sets(batch, self.aggs, nk)
             for i, a in enumerate(self.aggs):
+                if dsets[i] is not None:
+                    for gi_, vs in zip(gis.tolist(), set_lists[i]):
+                        dsets[i].setdefault(gi_, set()).update(
+                            _set_member(x) for x in vs)
+                    continue
                 vcol = batch.column(nk + 1 + 2 * i)
                 ccol = batch.column(nk + 2 + 2 * i).to_numpy(zero_copy_only=False).astype(np.int64)
                 if a["agg"] in ("count_star", "count"):
@@ -211,6 +226,20 @@ class DistMerger:
                             cur = merged.get(gi)
                             merged[gi] = v if cur is None else pick(cur, v)
                     str_minmax[i] = merged
+            if any(d is not None for d in dsets):
+                gathered = [None] * self.world
+                dist.all_gather_object(gathered, dsets)
+                for i in range(n_aggs):
+                    if dsets[i] is None:
+                        continue
+                    union: dict = {}
+                    for per_rank in gathered:
+                        for gi, vs in per_rank[i].items():
+                            # NaN members arrive as distinct objects per rank
+                            union.setdefault(gi, set()).update(
+                                "nan" if isinstance(x, float) and x != x else x
+                                for x in vs)
+                    dsets[i] = union
 
         presence = presence.cpu()
         counts = counts.cpu()
@@ -226,6 +255,8 @@ class DistMerger:
                 c = counts[gi, i].item()
                 if a["agg"] in ("count_star", "count"):
                     row.append(c)
+                elif dsets[i] is not None:
+                    row.append(len(dsets[i].get(gi, ())))
                 elif c == 0:
                     row.append(None)
                 elif a["agg"] == "sum":
@@ -245,5 +276,6 @@ class DistMerger:
                                else maxs[gi, i].item())
             out.append(row)
         if not self.group_by and not out:
-            out = [[0 if a["agg"] in ("count_star", "count") else None for a in self.aggs]]
+            out = [[0 if a["agg"] in ("count_star", "count", "count_distinct")
+                    else None for a in self.aggs]]
         return out

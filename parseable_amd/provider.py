@@ -295,13 +295,17 @@ class StagingScanner:
 
     def partial_batch(self, query):
         """-> pyarrow.RecordBatch in the partial-aggregate schema
-        [key..., __presence, agg_i, agg_i_count, ...] or None."""
+        [key..., __presence, agg_i, agg_i_count, ...] or None. A
+        count_distinct agg carries its distinct count in both slots and,
+        after all fixed columns, its `a{i}_set` list column — the same
+        positions the GPU leg's batch uses (distinct_set_columns)."""
         import pyarrow as pa
         import pyarrow.compute as pc
 
         group_by = query.get("group_by", [])
         aggs = query["select"]
         acc = {}
+        set_types = {}
         for tbl in self._tables():
             sel = tbl.filter(self._mask(tbl, query))
             if sel.num_rows == 0:
@@ -330,6 +334,19 @@ class StagingScanner:
                         c = c.cast(c.type.value_type)
                     if pa.types.is_timestamp(c.type):
                         c = c.cast(pa.int64())
+                    if a["agg"] == "count_distinct":
+                        # the GPU leg's list types: utf8 | int64 | float64
+                        if pa.types.is_integer(c.type):
+                            c = c.cast(pa.int64())
+                        elif pa.types.is_floating(c.type):
+                            c = c.cast(pa.float64())
+                        elif pa.types.is_large_string(c.type):
+                            c = c.cast(pa.string())
+                        elif not pa.types.is_string(c.type):
+                            raise GpuqError(
+                                "unsupported count_distinct column type "
+                                f"(utf8/i64/i32/f64/timestamp): {a['col']}")
+                        set_types[len(vals)] = c.type
                     vals.append(c.to_pylist())
             for r in range(sel.num_rows):
                 key = tuple(k[r] for k in keys)
@@ -344,6 +361,12 @@ class StagingScanner:
                         continue
                     v = vals[i][r]
                     if v is None:
+                        continue
+                    if a["agg"] == "count_distinct":
+                        if st[1][i] is None:
+                            st[1][i] = set()
+                        st[1][i].add(_set_member(v))
+                        st[2][i] = len(st[1][i])
                         continue
                     st[2][i] += 1
                     if a["agg"] == "count":
@@ -370,13 +393,25 @@ class StagingScanner:
         cols.append(pa.array([acc[k][0] for k in ks], type=pa.int64()))
         for i, a in enumerate(aggs):
             names.append(f"a{i}")
-            if a["agg"] in ("count_star", "count"):
+            if a["agg"] in COUNT_AGGS:
                 cols.append(pa.array([acc[k][2][i] for k in ks], type=pa.int64()))
             else:
                 cols.append(pa.array([acc[k][1][i] for k in ks]))
             names.append(f"a{i}_count")
             cols.append(pa.array([acc[k][2][i] for k in ks], type=pa.int64()))
+        for i, a in enumerate(aggs):
+            if a["agg"] != "count_distinct":
+                continue
+            names.append(f"a{i}_set")
+            cols.append(pa.array([sorted(acc[k][1][i] or ()) for k in ks],
+                                 type=pa.list_(set_types[i])))
         return pa.record_batch(cols, names=names)
+
+    def aggregate(self, query):
+        """Final rows of the staging leg alone (merge_partials over its one
+        partial batch): [key..., agg...] in the normalized order."""
+        b = self.partial_batch(query)
+        return merge_partials([b] if b is not None else [], query)
 
     def matching_rows(self, query):
         """Projection leg: matching staging rows [select_cols...]."""
@@ -908,10 +943,47 @@ def _col_list(col):
     return col.to_pylist()
 
 
+# aggregates whose result over no rows is 0, never NULL
+COUNT_AGGS = ("count_star", "count", "count_distinct")
+
+_NAN = float("nan")
+
+
+def _set_member(v):
+    """Distinct-set member for a value: every NaN is the one member the
+    engine's f64 normalisation makes it (a python set would keep each NaN
+    object apart); -0.0 and 0.0 already compare equal."""
+    return _NAN if isinstance(v, float) and v != v else v
+
+
+def distinct_set_columns(aggs, n_keys):
+    """{agg index: column index of its `agg{i}_set` list} in a partial batch:
+    the set columns follow all fixed columns, in agg order (include/gpuq.h,
+    gpuq_plan_execute)."""
+    base = n_keys + 1 + 2 * len(aggs)
+    out = {}
+    for i, a in enumerate(aggs):
+        if a["agg"] == "count_distinct":
+            out[i] = base + len(out)
+    return out
+
+
+def batch_distinct_sets(batch, aggs, n_keys):
+    """{agg index: per-row python lists of the batch's `agg{i}_set` column}"""
+    set_cols = distinct_set_columns(aggs, n_keys)
+    if set_cols and batch.num_columns < n_keys + 1 + 2 * len(aggs) + len(set_cols):
+        raise GpuqError("partial batch lacks the agg{i}_set columns of its "
+                        "count_distinct aggregates")
+    return {i: batch.column(ci).to_pylist() for i, ci in set_cols.items()}
+
+
 def merge_partials(batches, query):
     """Final merge of partial aggregate tables (cross-partition and
     cross-rank). Output rows match the oracle's normalized form:
-    [key..., agg...] sorted by key tuple, NULL keys last."""
+    [key..., agg...] sorted by key tuple, NULL keys last. count_distinct
+    does not merge by +: one partial's count is final, several partials
+    union their `agg{i}_set` lists per key and the union's size is the
+    result."""
     group_by = query.get("group_by", [])
     aggs = query["select"]
     nk = len(group_by)
@@ -951,7 +1023,9 @@ def merge_partials(batches, query):
     for b in batches:
         if b is None or b.num_rows == 0:
             continue
-        cols = [_col_list(b.column(i)) for i in range(b.num_columns)]
+        cols = [_col_list(b.column(i))
+                for i in range(nk + 1 + 2 * len(aggs))]
+        sets = batch_distinct_sets(b, aggs, nk)
         n = b.num_rows
         for r in range(n):
             key = tuple(cols[k][r] for k in range(nk))
@@ -964,6 +1038,11 @@ def merge_partials(batches, query):
             for i, a in enumerate(aggs):
                 v = cols[nk + 1 + 2 * i][r]
                 c = cols[nk + 2 + 2 * i][r]
+                if a["agg"] == "count_distinct":
+                    if st["vals"][i] is None:
+                        st["vals"][i] = set()
+                    st["vals"][i].update(_set_member(x) for x in sets[i][r])
+                    continue
                 if a["agg"] in ("count_star", "count"):
                     st["cnts"][i] += v
                     continue
@@ -987,6 +1066,8 @@ def merge_partials(batches, query):
         for i, a in enumerate(aggs):
             if a["agg"] in ("count_star", "count"):
                 row.append(st["cnts"][i])
+            elif a["agg"] == "count_distinct":
+                row.append(len(st["vals"][i] or ()))
             elif a["agg"] == "avg":
                 row.append(st["vals"][i] / st["cnts"][i]
                            if st["cnts"][i] > 0 else None)
@@ -995,7 +1076,7 @@ def merge_partials(batches, query):
         rows.append(row)
     rows.sort(key=lambda r: tuple(((1, "") if v is None else (0, v)) for v in r[: len(group_by)]))
     if not group_by and not rows:
-        rows = [[0 if a["agg"] in ("count_star", "count") else None for a in aggs]]
+        rows = [[0 if a["agg"] in COUNT_AGGS else None for a in aggs]]
     return rows
 
 
