@@ -1277,6 +1277,23 @@ extern "C" gpuq_plan* gpuq_plan_build(
   }
   if (plan->group_cols.size() > (size_t)MAX_KEYS || plan->aggs.size() > (size_t)MAX_AGGS)
     throw std::runtime_error("too many keys/aggregates");
+  // the value decoders read INT32, INT64 and DOUBLE (4- or 8-byte PLAIN,
+  // dictionary, delta for the ints) and BYTE_ARRAY; BOOLEAN's bit-packed
+  // values, FLOAT, INT96 and fixed-length byte arrays have no decoder, and
+  // the 8-byte copy would return garbage for them
+  for (const auto& c : plan->cols) {
+    if (c.is_bin || c.phys == -1) continue;
+    if (c.phys != PT_INT32 && c.phys != PT_INT64 && c.phys != PT_DOUBLE &&
+        c.phys != PT_BYTE_ARRAY) {
+      static const char* names[] = {"BOOLEAN", "INT32", "INT64", "INT96",
+                                    "FLOAT", "DOUBLE", "BYTE_ARRAY",
+                                    "FIXED_LEN_BYTE_ARRAY"};
+      throw std::runtime_error(
+          "unsupported column type " +
+          std::string(c.phys >= 0 && c.phys < 8 ? names[c.phys] : "?") +
+          " (INT32/INT64/DOUBLE/BYTE_ARRAY only): " + c.name);
+    }
+  }
 
   // --- select row groups (caller's list + footer-stats pruning) ---
   std::vector<RgRef> selected;

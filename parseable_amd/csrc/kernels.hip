@@ -946,23 +946,30 @@ k_plain_fixed(const uint8_t* __restrict__ dec, const DevPage* __restrict__ pages
   const uint8_t* def_start; uint32_t def_len; bool all_valid;
   const uint8_t* vals = def_levels(pg, dec + pg.dst_off, &def_start, &def_len, &all_valid);
   const uint32_t row0 = pg.row_start;
+  // INT32 pages hold 4-byte values, widened (sign-extended) to the 8-byte
+  // row arrays every consumer reads; INT64 / DOUBLE are copied bit for bit
+  const bool i32 = pg.phys == PT_INT32;
+  auto load = [&](uint32_t i) -> int64_t {
+    if (i32) {
+      int32_t v;
+      memcpy(&v, vals + (size_t)i * 4, 4);
+      return v;
+    }
+    int64_t v;
+    memcpy(&v, vals + (size_t)i * 8, 8);
+    return v;
+  };
   if (mode == 0 || mode == 2) {
     if (mode == 0 && !all_valid) return;
     uint32_t nv = pg.num_values;
     for (uint32_t i = lane; i < nv; i += WAVE) {
-      int64_t v;
-      memcpy(&v, vals + (size_t)i * 8, 8);
-      out[row0 + i] = v;
+      out[row0 + i] = load(i);
       if (valid) valid[row0 + i] = 1;
     }
   } else {
     if (all_valid) return;
     uint32_t nd = present[ids[pi]];   // dense to scratch; expansion follows
-    for (uint32_t i = lane; i < nd; i += WAVE) {
-      int64_t v;
-      memcpy(&v, vals + (size_t)i * 8, 8);
-      out[row0 + i] = v;
-    }
+    for (uint32_t i = lane; i < nd; i += WAVE) out[row0 + i] = load(i);
   }
 }
 
@@ -1535,6 +1542,50 @@ __global__ void k_ref_gather(const uint8_t* __restrict__ dec,
 //   Phase D: parallel value reconstruction.
 // LDS budget: 8192 miniblocks (262,144 values @ 32/miniblock).
 // ------------------------------------------------------------------
+// Delta i of a miniblock whose packed data starts at p, bit width bw in
+// 1..64: fetched from its absolute bit position, so no reader state carries
+// from one value to the next. A value spans at most 9 bytes: one unaligned
+// 8-byte load, and the 9th byte for the bits that window cannot hold. The
+// 8-byte load may run up to 7 bytes past the value (never selected; the
+// arena's over-read pad covers the last page, as for the index unpackers).
+__device__ __forceinline__ uint64_t delta_bits(const uint8_t* p, uint64_t i, int bw) {
+  const uint64_t bit = i * (uint64_t)bw;
+  const uint8_t* q = p + (bit >> 3);
+  const int sh = (int)(bit & 7);
+  uint64_t lo;
+  __builtin_memcpy(&lo, q, 8);
+  uint64_t v = lo >> sh;
+  if (sh + bw > 64) v |= (uint64_t)q[8] << (64 - sh);   // implies sh >= 1
+  return bw >= 64 ? v : (v & ((1ull << bw) - 1));
+}
+// Sequential reader over one miniblock's deltas. Widths up to 56 stream
+// through a 64-bit window: a byte is loaded only while nbits < bw <= 56, so
+// it lands at bit 55 or below and nothing is shifted out. Wider values would
+// spill past bit 63 on such a load (it lost the next value's low bits at
+// widths 59 and 61-63, and the bw == 64 shift was undefined); they are
+// fetched by position instead.
+struct DeltaMiniReader {
+  const uint8_t* base;
+  const uint8_t* p;
+  int bw;
+  uint64_t acc = 0, i = 0;
+  int nbits = 0;
+  __device__ __forceinline__ DeltaMiniReader(const uint8_t* b, int w)
+      : base(b), p(b), bw(w) {}
+  __device__ __forceinline__ uint64_t next() {
+    if (bw == 0) return 0;
+    if (bw > 56) return delta_bits(base, i++, bw);
+    while (nbits < bw) { acc |= (uint64_t)(*p++) << nbits; nbits += 8; }
+    uint64_t d = acc & ((1ull << bw) - 1);
+    acc >>= bw; nbits -= bw;
+    return d;
+  }
+};
+// INT32 columns: the writer's deltas wrap at 32 bits. The 64-bit wrapping
+// sum truncated to 32 bits is that sum, so narrowing happens at the store.
+__device__ __forceinline__ int64_t delta_out(const DevPage& pg, uint64_t v) {
+  return pg.phys == PT_INT32 ? (int64_t)(int32_t)(uint32_t)v : (int64_t)v;
+}
 #define MAX_MB 8192
 #define MAX_BLK 2048
 #define DELTA_T 256
@@ -1568,37 +1619,45 @@ k_delta_i64(const uint8_t* __restrict__ dec, const DevPage* __restrict__ pages,
     auto rv = [&]() { uint64_t v = 0; int sh = 0; for (;;) { uint8_t b = *q++; v |= (uint64_t)(b & 0x7f) << sh; if (!(b & 0x80)) return v; sh += 7; } };
     auto rz = [&]() { uint64_t v = rv(); return (int64_t)(v >> 1) ^ -(int64_t)(v & 1); };
     uint64_t blk = rv(), mpb = rv(), total = rv();
-    int64_t value = rz();
+    uint64_t value = (uint64_t)rz();
+    if (mpb == 0 || mpb > 256 || (blk / mpb) % 8 || (blk / mpb) == 0) {
+      atomicExch(d_error, ERR_DELTA);
+      return;
+    }
     uint64_t per_mini = blk / mpb;
     uint64_t emitted = 0;
-    int64_t cur_md = 0; uint8_t bws[256]; uint64_t mb = 0, in_mb = 0;
-    uint64_t acc = 0; int nbits = 0;
+    // block state: min_delta, the bit-width bytes, and the current
+    // miniblock's data start / width / position within it
+    uint64_t cur_md = 0; const uint8_t* bws = q; const uint8_t* mbp = q;
+    uint64_t mb = 0, in_mb = 0; int bw = 0;
     for (uint32_t r = 0; r < pg.num_values; r++) {
       if (!def.next()) { if (valid) valid[pg.row_start + r] = 0; continue; }
-      int64_t v;
-      if (emitted == 0) v = value;
-      else {
+      if (emitted >= total) {  // more present rows than encoded values
+        atomicExch(d_error, ERR_DELTA);
+        return;
+      }
+      if (emitted != 0) {
         if (((emitted - 1) % (per_mini * mpb)) == 0) {  // new block
-          cur_md = rz();
-          for (uint64_t m = 0; m < mpb; m++) bws[m] = *q++;
-          mb = 0; in_mb = 0; acc = 0; nbits = 0;
+          cur_md = (uint64_t)rz();
+          bws = q; q += mpb;
+          mb = 0; in_mb = 0; mbp = q; bw = bws[0];
+          if (bw > 64) { atomicExch(d_error, ERR_DELTA); return; }
         }
-        int bw = bws[mb];
-        uint64_t d = 0;
-        if (bw) {
-          while (nbits < bw) { acc |= (uint64_t)(*q++) << nbits; nbits += 8; }
-          d = (bw >= 64) ? acc : (acc & ((1ull << bw) - 1));
-          acc >>= bw; nbits -= bw;
+        uint64_t d = bw ? delta_bits(mbp, in_mb, bw) : 0;
+        value += cur_md + d;
+        if (++in_mb == per_mini) {
+          mbp += (per_mini * (uint64_t)bw) / 8;
+          q = mbp;              // the next block header follows the last miniblock
+          in_mb = 0; mb++;
+          // widths of miniblocks past the last value are unspecified
+          bw = (mb < mpb && emitted + 1 < total) ? bws[mb] : 0;
+          if (bw > 64) { atomicExch(d_error, ERR_DELTA); return; }
         }
-        value += cur_md + (int64_t)d;
-        v = value;
-        if (++in_mb == per_mini) { in_mb = 0; mb++; acc = 0; nbits = 0; }
       }
       emitted++;
-      out[pg.row_start + r] = v;
+      out[pg.row_start + r] = delta_out(pg, value);
       if (valid) valid[pg.row_start + r] = 1;
     }
-    (void)total;
     return;
   }
 
@@ -1609,8 +1668,12 @@ k_delta_i64(const uint8_t* __restrict__ dec, const DevPage* __restrict__ pages,
   auto rz = [&]() { uint64_t v = rv(); return (int64_t)(v >> 1) ^ -(int64_t)(v & 1); };
   uint64_t blk_size = rv(), mpb = rv(), total = rv();
   int64_t first = rz();
+  if (mpb == 0 || mpb > 256 || blk_size / mpb == 0) {
+    if (lane == 0) atomicExch(d_error, ERR_DELTA);
+    return;
+  }
   uint64_t per_mini = blk_size / mpb;
-  if (per_mini % 8 || total > pg.num_values || mpb > 256) {
+  if (per_mini % 8 || total > pg.num_values) {
     if (lane == 0) atomicExch(d_error, ERR_DELTA);
     return;
   }
@@ -1624,6 +1687,7 @@ k_delta_i64(const uint8_t* __restrict__ dec, const DevPage* __restrict__ pages,
   // walk blocks redundantly; every lane records into LDS identically
   {
     uint32_t mb = 0;
+    bool bad_bw = false;
     for (uint32_t b = 0; b < n_blk; b++) {
       int64_t md = rz();
       if (lane == 0) blk_md[b] = md;
@@ -1634,8 +1698,13 @@ k_delta_i64(const uint8_t* __restrict__ dec, const DevPage* __restrict__ pages,
           mb_off[mb] = (uint32_t)(q - vals);
           mb_bw[mb] = bws[m];
         }
+        bad_bw |= bws[m] > 64;
         q += (per_mini * bws[m]) / 8;
       }
+    }
+    if (bad_bw) {  // uniform: every lane walked the same headers
+      if (lane == 0) atomicExch(d_error, ERR_DELTA);
+      return;
     }
   }
   __syncthreads();
@@ -1647,31 +1716,23 @@ k_delta_i64(const uint8_t* __restrict__ dec, const DevPage* __restrict__ pages,
     int64_t md = blk_md[m / (uint32_t)mpb];
     uint64_t cnt = per_mini;
     if ((uint64_t)(m + 1) * per_mini > n_deltas) cnt = n_deltas - (uint64_t)m * per_mini;
-    int64_t s = 0;
-    uint64_t acc = 0; int nbits = 0;
-    for (uint64_t i = 0; i < cnt; i++) {
-      uint64_t dv = 0;
-      if (bw) {
-        while (nbits < bw) { acc |= (uint64_t)(*p++) << nbits; nbits += 8; }
-        dv = (bw >= 64) ? acc : (acc & ((1ull << bw) - 1));
-        acc >>= bw; nbits -= bw;
-      }
-      s += md + (int64_t)dv;
-    }
-    mb_sum[m] = s;
+    uint64_t s = 0;   // wrapping arithmetic throughout: unsigned
+    DeltaMiniReader rd(p, bw);
+    for (uint64_t i = 0; i < cnt; i++) s += (uint64_t)md + rd.next();
+    mb_sum[m] = (int64_t)s;
   }
   __syncthreads();
 
   // Phase C: serial exclusive scan of miniblock sums -> starting value
   if (lane == 0) {
-    int64_t run = first;
-    for (uint32_t m = 0; m < n_mb; m++) { int64_t s = mb_sum[m]; mb_sum[m] = run; run += s; }
+    uint64_t run = (uint64_t)first;
+    for (uint32_t m = 0; m < n_mb; m++) { uint64_t s = (uint64_t)mb_sum[m]; mb_sum[m] = (int64_t)run; run += s; }
   }
   __syncthreads();
 
   // Phase D: reconstruct values
   if (total) {
-    if (lane == 0) { out[pg.row_start] = first; if (valid) valid[pg.row_start] = 1; }
+    if (lane == 0) { out[pg.row_start] = delta_out(pg, (uint64_t)first); if (valid) valid[pg.row_start] = 1; }
   }
   for (uint32_t m = lane; m < n_mb; m += DELTA_T) {
     const uint8_t* p = vals + mb_off[m];
@@ -1679,18 +1740,12 @@ k_delta_i64(const uint8_t* __restrict__ dec, const DevPage* __restrict__ pages,
     int64_t md = blk_md[m / (uint32_t)mpb];
     uint64_t cnt = per_mini;
     if ((uint64_t)(m + 1) * per_mini > n_deltas) cnt = n_deltas - (uint64_t)m * per_mini;
-    int64_t v = mb_sum[m];
-    uint64_t acc = 0; int nbits = 0;
+    uint64_t v = (uint64_t)mb_sum[m];
     uint64_t base = 1 + (uint64_t)m * per_mini;  // value index of first delta output
+    DeltaMiniReader rd(p, bw);
     for (uint64_t i = 0; i < cnt; i++) {
-      uint64_t dv = 0;
-      if (bw) {
-        while (nbits < bw) { acc |= (uint64_t)(*p++) << nbits; nbits += 8; }
-        dv = (bw >= 64) ? acc : (acc & ((1ull << bw) - 1));
-        acc >>= bw; nbits -= bw;
-      }
-      v += md + (int64_t)dv;
-      out[pg.row_start + base + i] = v;
+      v += (uint64_t)md + rd.next();
+      out[pg.row_start + base + i] = delta_out(pg, v);
       if (valid) valid[pg.row_start + base + i] = 1;
     }
   }
