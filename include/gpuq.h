@@ -283,8 +283,8 @@ enum {
 };
 /* or'ed onto the plan mode: no device work, no session needed. `out` gets
  * the host scalar decoders' bytes; with REPLAY it gets a serial host replay
- * of the planned device records instead (segments, literal copies, inline /
- * resolved / windowed matches, in launch order). */
+ * of the planned device records instead (segments, sequence tiles, literal
+ * copies, resolved / windowed matches, in launch order). */
 #define GPUQ_DECOMP_HOST_ONLY   0x100
 #define GPUQ_DECOMP_HOST_REPLAY 0x200
 
@@ -306,6 +306,9 @@ typedef struct {
   uint32_t n_res_lane, n_res_wave;
   uint32_t n_pieces;
   uint32_t n_backrefs, n_far;   /* windowed records; of those, far branch */
+  uint32_t n_tile, n_tile_rec;  /* litpar sequence tiles and their records:
+                                   every n_lit_lane run and n_inl match is
+                                   in one, an adjacent pair sharing it */
 } gpuq_decomp_stats;
 
 /* The blocks are packed back to back into the raw buffer after `raw_lead`

@@ -67,7 +67,8 @@ class GpuqDecompStats(C.Structure):
     _fields_ = [("mode", C.c_int32)] + [
         (n, C.c_uint32) for n in (
             "n_seq", "n_segs", "n_big", "n_lit_lane", "n_lit_wave", "n_inl",
-            "n_res_lane", "n_res_wave", "n_pieces", "n_backrefs", "n_far")
+            "n_res_lane", "n_res_wave", "n_pieces", "n_backrefs", "n_far",
+            "n_tile", "n_tile_rec")
     ]
 
 

@@ -46,16 +46,24 @@ struct DevBrRes {      // literal-resolved record (absolute dec offsets)
   uint32_t piece_start, piece_n;
 };
 struct DevPiece { uint64_t src; uint32_t len; uint32_t _pad; };
-// litpar literal copy: raw[src..src+len) -> dec[dst..dst+len), PACKED to
-// 16 B — at 1 B-row scale these record streams are the largest kernel
-// fetch (PMC: 6-8 GB/launch at 24 B each), so the layout is the traffic.
+// litpar literal copy of a run > 256 B (k_lit_wave; shorter runs ride the
+// sequence records below): raw[src..src+len) -> dec[dst..dst+len).
 // a = src | len << 40 (arenas < 1 TB so offsets fit 40 bits; literal runs
 // < 2^24); b = dst.
 struct DevLit { uint64_t a, b; };
-// resolved match whose pattern (<= 8 bytes) the host inlined from the
-// compressed literal bytes: write-only, no scattered pattern reads.
-// meta = dst | len << 40 | period << 52 (len <= 256, period <= 8).
-struct DevBrInl { uint64_t meta, pat; };
+// litpar sequence record: a literal run (<= 256 B, copied from raw) and the
+// match that follows it in the output, whose pattern (<= 8 bytes) the host
+// inlined from the compressed literal bytes — no scattered pattern reads.
+// a = raw_src | lit_len << 40 (9 bits) | match_len << 49 (9 bits) |
+//     period << 58 (4 bits, 1..8 when match_len > 0); either part may be
+// empty. There is no dst: the records of a tile produce its output span
+// back to back, so a record's offset is the prefix sum of the lengths.
+struct DevSeq { uint64_t a, pat; };
+constexpr uint32_t SEQ_TILE_RECS = 256;     // k_seq_tile block size
+constexpr uint32_t SEQ_TILE_BYTES = 16384;  // k_seq_tile LDS stage
+// records [rec0, rec0 + n_rec) produce exactly dec[dst0, dst0 + out_len);
+// n_rec <= SEQ_TILE_RECS, out_len <= SEQ_TILE_BYTES.
+struct DevSeqTile { uint64_t dst0; uint64_t rec0; uint32_t n_rec; uint32_t out_len; };
 // contains window: a value-aligned run of consecutive non-null values of one
 // PLAIN byte-array page, <= CWIN bytes total (or a single oversized value,
 // nbytes > CWIN). Host builds these at load time by decompressing the page

@@ -274,8 +274,9 @@ struct Partition {
   // literal-resolved records (single launch; meta.cpp lz4_walk)
   std::vector<DevBrRes> res_lane, res_wave;
   std::vector<DevPiece> piece_pool;
-  std::vector<DevBrInl> brinl;       // host-inlined <=8B patterns (litpar)
-  std::vector<DevLit> lits_lane, lits_wave;   // litpar pages (meta.h)
+  std::vector<DevSeq> seqs;          // litpar sequence records (dev_types.h)
+  std::vector<DevSeqTile> tiles;
+  std::vector<DevLit> lits_wave;     // litpar literal runs > 256 B
   // contains windows (host length-chain walk at load time; dev_types.h)
   std::vector<DevCWin> cwins;
   std::vector<uint16_t> cstarts;
@@ -324,9 +325,9 @@ struct Partition {
   DevPageBr* d_pagebrs = nullptr;
   DevBrRes* d_res_lane = nullptr;
   DevBrRes* d_res_wave = nullptr;
-  DevBrInl* d_brinl = nullptr;
+  DevSeq* d_seqs = nullptr;
+  DevSeqTile* d_tiles = nullptr;
   DevPiece* d_piece_pool = nullptr;
-  DevLit* d_lits_lane = nullptr;
   DevLit* d_lits_wave = nullptr;
   DevCWin* d_cwins = nullptr;
   uint16_t* d_cstarts = nullptr;
@@ -815,8 +816,9 @@ struct DecompRecs {
   std::vector<DevPageBr> pagebrs;
   std::vector<DevBrRes> res_lane, res_wave;
   std::vector<DevPiece> piece_pool;
-  std::vector<DevBrInl> brinl;
-  std::vector<DevLit> lits_lane, lits_wave;
+  std::vector<DevSeq> seqs;          // litpar sequence records ...
+  std::vector<DevSeqTile> tiles;     // ... and the tiles that own them
+  std::vector<DevLit> lits_wave;     // litpar literal runs > 256 B
   // host-decompressed page images staged straight into the dec arena
   // (snappy piece-explosion fallback — no serial snappy device kernel)
   std::vector<std::pair<uint64_t, std::vector<uint8_t>>> himgs;
@@ -911,12 +913,6 @@ void plan_decomp_page(DecompRecs& cb, int codec, const uint8_t* praw,
     d2.big = sg.big;
     cb.segs.push_back(d2);
   }
-  for (const auto& lt : lp.lits) {
-    DevLit dl{(src_abs + lt.src) | ((uint64_t)lt.len << 40),
-              dst_abs + lt.dst};
-    (lt.len <= 256 ? cb.lits_lane : cb.lits_wave).push_back(dl);
-    if (st) (lt.len <= 256 ? st->n_lit_lane : st->n_lit_wave)++;
-  }
   if (lp.fallback) {
     // piece explosion: serial windowed wave per page
     DevPageBr pb{(uint32_t)cb.brs.size(), (uint32_t)lp.backrefs.size()};
@@ -928,60 +924,116 @@ void plan_decomp_page(DecompRecs& cb, int codec, const uint8_t* praw,
         st->n_far += (br.dst - br.src) + br.len > BR_FAR;
       }
     }
-  } else if (!lp.resolved.empty()) {
-    // litpar pieces are literal-backed: the host can read any
-    // pattern of <= 8 bytes straight from the compressed stream
-    // and inline it — the resolver then never touches dec sources
-    auto lit_bytes = [&](uint32_t src, uint32_t len,
-                         uint8_t* out) -> bool {
-      const auto& Ls = lp.lits;   // dst-ascending by construction
-      size_t lo = 0, hi = Ls.size();
-      while (lo < hi) {
-        size_t mid = (lo + hi) / 2;
-        if (Ls[mid].dst <= src) lo = mid + 1;
-        else hi = mid;
+    return;
+  }
+  // litpar pieces are literal-backed: the host can read any
+  // pattern of <= 8 bytes straight from the compressed stream
+  // and inline it — the replay then never touches dec sources
+  auto lit_bytes = [&](uint32_t src, uint32_t len, uint8_t* out) -> bool {
+    const auto& Ls = lp.lits;   // dst-ascending by construction
+    size_t lo = 0, hi = Ls.size();
+    while (lo < hi) {
+      size_t mid = (lo + hi) / 2;
+      if (Ls[mid].dst <= src) lo = mid + 1;
+      else hi = mid;
+    }
+    if (lo == 0) return false;
+    const Lz4Lit& L = Ls[lo - 1];
+    if (src < L.dst || src + len > L.dst + L.len) return false;
+    std::memcpy(out, praw + L.src + (src - L.dst), len);
+    return true;
+  };
+  auto try_inline = [&](const Lz4Resolved& rr, uint64_t* pat,
+                        uint32_t* period) -> bool {
+    uint32_t pat_len = 0;
+    for (uint32_t k = 0; k < rr.piece_n; k++)
+      pat_len += lp.pieces[rr.piece_start + k].len;
+    if (!lp.litpar || pat_len == 0 || pat_len > 8 || rr.len > 256)
+      return false;
+    uint8_t buf[8] = {0};
+    uint32_t o = 0;
+    for (uint32_t k = 0; k < rr.piece_n; k++) {
+      const Lz4Piece& pc = lp.pieces[rr.piece_start + k];
+      if (!lit_bytes(pc.src, pc.len, buf + o)) return false;
+      o += pc.len;
+    }
+    std::memcpy(pat, buf, 8);
+    *period = pat_len;
+    return true;
+  };
+  auto push_resolved = [&](const Lz4Resolved& rr) {
+    uint32_t ps = (uint32_t)cb.piece_pool.size();
+    for (uint32_t k = 0; k < rr.piece_n; k++) {
+      const Lz4Piece& pc = lp.pieces[rr.piece_start + k];
+      cb.piece_pool.push_back({dst_abs + pc.src, pc.len, 0});
+    }
+    DevBrRes rec{dst_abs + rr.dst, rr.len, rr.off, ps, rr.piece_n};
+    if (rr.len <= 256) cb.res_lane.push_back(rec);
+    else cb.res_wave.push_back(rec);
+    if (st) {
+      (rr.len <= 256 ? st->n_res_lane : st->n_res_wave)++;
+      st->n_pieces += rr.piece_n;
+    }
+  };
+  // sequence tiles: a short literal run and the inlinable match behind it
+  // share one record, and records with contiguous output share a tile (the
+  // tile stays open across calls only through `open`, so it ends with the
+  // page). Anything else interrupts the output run and so closes the tile.
+  bool open = false;
+  auto push_seq = [&](uint64_t dst, const DevSeq& rec, uint32_t len) {
+    if (open) {
+      const DevSeqTile& t = cb.tiles.back();
+      if (t.dst0 + t.out_len != dst || t.n_rec == SEQ_TILE_RECS ||
+          t.out_len + len > SEQ_TILE_BYTES)
+        open = false;
+    }
+    if (!open) {
+      cb.tiles.push_back({dst, (uint64_t)cb.seqs.size(), 0, 0});
+      open = true;
+      if (st) st->n_tile++;
+    }
+    cb.seqs.push_back(rec);
+    cb.tiles.back().n_rec++;
+    cb.tiles.back().out_len += len;
+    if (st) st->n_tile_rec++;
+  };
+  auto match_bits = [](uint32_t len, uint32_t period) {
+    return ((uint64_t)len << 49) | ((uint64_t)period << 58);
+  };
+  // lits and resolved are each dst-ascending and together tile the page
+  size_t li = 0, ri = 0;
+  const size_t nl = lp.lits.size(), nr = lp.resolved.size();
+  while (li < nl || ri < nr) {
+    uint64_t pat = 0;
+    uint32_t period = 0;
+    if (ri >= nr || (li < nl && lp.lits[li].dst < lp.resolved[ri].dst)) {
+      const Lz4Lit& lt = lp.lits[li++];
+      if (lt.len > 256) {
+        cb.lits_wave.push_back({(src_abs + lt.src) | ((uint64_t)lt.len << 40),
+                                dst_abs + lt.dst});
+        if (st) st->n_lit_wave++;
+        continue;
       }
-      if (lo == 0) return false;
-      const Lz4Lit& L = Ls[lo - 1];
-      if (src < L.dst || src + len > L.dst + L.len) return false;
-      std::memcpy(out, praw + L.src + (src - L.dst), len);
-      return true;
-    };
-    for (const auto& rr : lp.resolved) {
-      uint32_t pat_len = 0;
-      for (uint32_t k = 0; k < rr.piece_n; k++)
-        pat_len += lp.pieces[rr.piece_start + k].len;
-      if (lp.litpar && pat_len > 0 && pat_len <= 8 && rr.len <= 256) {
-        uint8_t buf[8] = {0};
-        uint32_t o = 0;
-        bool ok = true;
-        for (uint32_t k = 0; k < rr.piece_n && ok; k++) {
-          const Lz4Piece& pc = lp.pieces[rr.piece_start + k];
-          ok = lit_bytes(pc.src, pc.len, buf + o);
-          o += pc.len;
-        }
-        if (ok) {
-          uint64_t pat;
-          std::memcpy(&pat, buf, 8);
-          cb.brinl.push_back({(dst_abs + rr.dst) |
-                                  ((uint64_t)rr.len << 40) |
-                                  ((uint64_t)pat_len << 52),
-                              pat});
-          if (st) st->n_inl++;
-          continue;
-        }
+      if (st) st->n_lit_lane++;
+      DevSeq rec{(src_abs + lt.src) | ((uint64_t)lt.len << 40), 0};
+      uint32_t len = lt.len;
+      if (ri < nr && lp.resolved[ri].dst == lt.dst + lt.len &&
+          try_inline(lp.resolved[ri], &pat, &period)) {
+        const Lz4Resolved& rr = lp.resolved[ri++];
+        rec.a |= match_bits(rr.len, period);
+        rec.pat = pat;
+        len += rr.len;
+        if (st) st->n_inl++;
       }
-      uint32_t ps = (uint32_t)cb.piece_pool.size();
-      for (uint32_t k = 0; k < rr.piece_n; k++) {
-        const Lz4Piece& pc = lp.pieces[rr.piece_start + k];
-        cb.piece_pool.push_back({dst_abs + pc.src, pc.len, 0});
-      }
-      DevBrRes rec{dst_abs + rr.dst, rr.len, rr.off, ps, rr.piece_n};
-      if (rr.len <= 256) cb.res_lane.push_back(rec);
-      else cb.res_wave.push_back(rec);
-      if (st) {
-        (rr.len <= 256 ? st->n_res_lane : st->n_res_wave)++;
-        st->n_pieces += rr.piece_n;
+      push_seq(dst_abs + lt.dst, rec, len);
+    } else {
+      const Lz4Resolved& rr = lp.resolved[ri++];
+      if (try_inline(rr, &pat, &period)) {
+        push_seq(dst_abs + rr.dst, {src_abs | match_bits(rr.len, period), pat},
+                 rr.len);
+        if (st) st->n_inl++;
+      } else {
+        push_resolved(rr);
       }
     }
   }
@@ -992,9 +1044,9 @@ struct DecompDev {
   const uint8_t* d_raw;
   uint8_t* d_dec;
   const DevSeg* d_segs; int n_segs;
-  const DevLit* d_lits_lane; int64_t n_lits_lane;
+  const DevSeq* d_seqs;
+  const DevSeqTile* d_tiles; int n_tiles;
   const DevLit* d_lits_wave; int n_lits_wave;
-  const DevBrInl* d_brinl; int64_t n_brinl;
   const DevBrRes* d_res_lane; int64_t n_res_lane;
   const DevBrRes* d_res_wave; int n_res_wave;
   const DevPiece* d_piece_pool;
@@ -1006,13 +1058,14 @@ struct DecompDev {
 // decompress: parallel segments, then ordered backref resolution
 void launch_decompress(hipStream_t st, const DecompDev& d) {
   launch_lz4_seg(st, d.d_raw, d.d_dec, d.d_segs, d.n_segs, d.d_err);
-  // litpar pages: flat literal copies (independent of the segment pass)
-  launch_lit_lane(st, d.d_raw, d.d_dec, d.d_lits_lane, d.n_lits_lane);
+  // litpar pages: sequence tiles (short literals + inlined matches) and
+  // flat long-literal copies, independent of the segment pass
+  launch_seq_tile(st, d.d_raw, d.d_dec, d.d_seqs, d.d_tiles, d.n_tiles);
   launch_lit_wave(st, d.d_raw, d.d_dec, d.d_lits_wave, d.n_lits_wave);
   // deferred-match resolution: host-resolved records are independent —
-  // one launch each (kernel boundary after phase 1 gives coherence);
-  // piece-explosion pages fall back to the serial windowed wave
-  launch_brres_inl(st, d.d_dec, d.d_brinl, d.n_brinl);
+  // one launch each (kernel boundary after phase 1 gives coherence; their
+  // pieces read bytes the tiles produce); piece-explosion pages fall back
+  // to the serial windowed wave
   launch_brres_lane(st, d.d_dec, d.d_res_lane, d.d_piece_pool, d.n_res_lane);
   launch_brres_wave(st, d.d_dec, d.d_res_wave, d.d_piece_pool, d.n_res_wave);
   launch_lz4_backrefs(st, d.d_dec, d.d_brs, d.d_pagebrs, d.n_pagebrs);
@@ -1815,8 +1868,8 @@ extern "C" gpuq_plan* gpuq_plan_build(
       const size_t nc = cbs.size();
       std::vector<size_t> o_pages(nc + 1, 0), o_segs(nc + 1, 0),
           o_brs(nc + 1, 0), o_pagebrs(nc + 1, 0), o_rl(nc + 1, 0),
-          o_rw(nc + 1, 0), o_pp(nc + 1, 0), o_bi(nc + 1, 0),
-          o_ll(nc + 1, 0), o_lw(nc + 1, 0);
+          o_rw(nc + 1, 0), o_pp(nc + 1, 0), o_sq(nc + 1, 0),
+          o_ti(nc + 1, 0), o_lw(nc + 1, 0);
       for (size_t i = 0; i < nc; i++) {
         const auto& cb = cbs[i];
         o_pages[i + 1] = o_pages[i] + cb.pages.size();
@@ -1826,8 +1879,8 @@ extern "C" gpuq_plan* gpuq_plan_build(
         o_rl[i + 1] = o_rl[i] + cb.res_lane.size();
         o_rw[i + 1] = o_rw[i] + cb.res_wave.size();
         o_pp[i + 1] = o_pp[i] + cb.piece_pool.size();
-        o_bi[i + 1] = o_bi[i] + cb.brinl.size();
-        o_ll[i + 1] = o_ll[i] + cb.lits_lane.size();
+        o_sq[i + 1] = o_sq[i] + cb.seqs.size();
+        o_ti[i + 1] = o_ti[i] + cb.tiles.size();
         o_lw[i + 1] = o_lw[i] + cb.lits_wave.size();
       }
       part.pages.resize(o_pages[nc]);
@@ -1837,8 +1890,8 @@ extern "C" gpuq_plan* gpuq_plan_build(
       part.res_lane.resize(o_rl[nc]);
       part.res_wave.resize(o_rw[nc]);
       part.piece_pool.resize(o_pp[nc]);
-      part.brinl.resize(o_bi[nc]);
-      part.lits_lane.resize(o_ll[nc]);
+      part.seqs.resize(o_sq[nc]);
+      part.tiles.resize(o_ti[nc]);
       part.lits_wave.resize(o_lw[nc]);
       parallel_for(nc, [&](size_t i) {
         auto& cb = cbs[i];
@@ -1866,10 +1919,13 @@ extern "C" gpuq_plan* gpuq_plan_build(
           r2.piece_start += piece_base;
           part.res_wave[o_rw[i] + j] = r2;
         }
-        std::copy(cb.brinl.begin(), cb.brinl.end(),
-                  part.brinl.begin() + o_bi[i]);
-        std::copy(cb.lits_lane.begin(), cb.lits_lane.end(),
-                  part.lits_lane.begin() + o_ll[i]);
+        std::copy(cb.seqs.begin(), cb.seqs.end(),
+                  part.seqs.begin() + o_sq[i]);
+        for (size_t j = 0; j < cb.tiles.size(); j++) {
+          DevSeqTile t2 = cb.tiles[j];
+          t2.rec0 += o_sq[i];
+          part.tiles[o_ti[i] + j] = t2;
+        }
         std::copy(cb.lits_wave.begin(), cb.lits_wave.end(),
                   part.lits_wave.begin() + o_lw[i]);
       });
@@ -2200,13 +2256,26 @@ extern "C" gpuq_plan* gpuq_plan_build(
     }
     for (size_t p = 0; p < plan->parts.size(); p++) {
       const auto& pt = plan->parts[p];
+      // matches an 8 B record could hold: minimal period <= 3
+      size_t period_le3 = 0;
+      for (const DevSeq& r : pt.seqs) {
+        const uint32_t ml = (uint32_t)(r.a >> 49) & 0x1ff;
+        const uint32_t n = std::min(ml, (uint32_t)(r.a >> 58));
+        for (uint32_t q = 1; q <= 3 && ml; q++) {
+          bool ok = true;
+          for (uint32_t j = q; j < n && ok; j++)
+            ok = (uint8_t)(r.pat >> (j * 8)) == (uint8_t)(r.pat >> ((j - q) * 8));
+          if (ok) { period_le3++; break; }
+        }
+      }
       fprintf(stderr,
               "[gpuq plan] part %zu: rows=%lld chunks=%zu pages=%zu segs=%zu "
-              "lits=%zu/%zu brinl=%zu res=%zu/%zu pieces=%zu raw=%.2fGB "
+              "tiles=%zu tile_recs=%zu period_le3=%zu lits_wave=%zu "
+              "res=%zu/%zu pieces=%zu raw=%.2fGB "
               "dec=%.2fGB cwins=%zu\n",
               p, (long long)pt.n_rows, pt.chunks.size(), pt.pages.size(),
-              pt.segs.size(), pt.lits_lane.size(), pt.lits_wave.size(),
-              pt.brinl.size(), pt.res_lane.size(), pt.res_wave.size(),
+              pt.segs.size(), pt.tiles.size(), pt.seqs.size(), period_le3,
+              pt.lits_wave.size(), pt.res_lane.size(), pt.res_wave.size(),
               pt.piece_pool.size(), pt.raw_bytes / 1e9, pt.dec_bytes / 1e9,
               pt.cwins.size());
     }
@@ -2485,12 +2554,12 @@ extern "C" int32_t gpuq_plan_load(gpuq_plan* plan, int32_t pi) try {
               (void**)&part.d_res_wave);
   upload_pool(part.piece_pool.data(), part.piece_pool.size() * sizeof(DevPiece),
               (void**)&part.d_piece_pool);
-  upload_pool(part.lits_lane.data(), part.lits_lane.size() * sizeof(DevLit),
-              (void**)&part.d_lits_lane);
+  upload_pool(part.seqs.data(), part.seqs.size() * sizeof(DevSeq),
+              (void**)&part.d_seqs);
+  upload_pool(part.tiles.data(), part.tiles.size() * sizeof(DevSeqTile),
+              (void**)&part.d_tiles);
   upload_pool(part.lits_wave.data(), part.lits_wave.size() * sizeof(DevLit),
               (void**)&part.d_lits_wave);
-  upload_pool(part.brinl.data(), part.brinl.size() * sizeof(DevBrInl),
-              (void**)&part.d_brinl);
   upload_pool(part.cwins.data(), part.cwins.size() * sizeof(DevCWin),
               (void**)&part.d_cwins);
   upload_pool(part.cstarts.data(), part.cstarts.size() * sizeof(uint16_t),
@@ -3017,9 +3086,8 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
   launch_decompress(st, DecompDev{
       part.d_raw, part.d_dec,
       part.d_segs, (int)part.segs.size(),
-      part.d_lits_lane, (int64_t)part.lits_lane.size(),
+      part.d_seqs, part.d_tiles, (int)part.tiles.size(),
       part.d_lits_wave, (int)part.lits_wave.size(),
-      part.d_brinl, (int64_t)part.brinl.size(),
       part.d_res_lane, (int64_t)part.res_lane.size(),
       part.d_res_wave, (int)part.res_wave.size(),
       part.d_piece_pool, part.d_brs,
@@ -4020,8 +4088,8 @@ gpuq_plan::~gpuq_plan() {
     for (auto* ptr : part.d_gid2pair) F(ptr); F(part.d_needle); F(part.d_all_ids);
     F(part.d_rowof); F(part.d_rank); F(part.d_scr);
     F(part.d_present); F(part.d_tmpvalid);
-    F(part.d_lits_lane); F(part.d_lits_wave);
-    F(part.d_cwins); F(part.d_cstarts); F(part.d_brinl);
+    F(part.d_seqs); F(part.d_tiles); F(part.d_lits_wave);
+    F(part.d_cwins); F(part.d_cstarts);
     F(part.d_segs); F(part.d_brs); F(part.d_pagebrs);
     F(part.d_res_lane); F(part.d_res_wave); F(part.d_piece_pool);
     F(part.d_keys); F(part.d_keys_sorted); F(part.d_rows);
@@ -4089,16 +4157,23 @@ void replay_decompress(const uint8_t* raw, uint8_t* dec, const DecompRecs& R) {
     }
     if (d != sg.out_len) throw std::runtime_error("replay: segment size mismatch");
   }
-  for (const auto* lits : {&R.lits_lane, &R.lits_wave})
-    for (const DevLit& L : *lits)
-      std::memcpy(dec + L.b, raw + (L.a & ((1ull << 40) - 1)), L.a >> 40);
-  for (const DevBrInl& r : R.brinl) {
-    uint8_t* o = dec + (r.meta & ((1ull << 40) - 1));
-    uint32_t len = (uint32_t)(r.meta >> 40) & 0xfff;
-    uint32_t period = (uint32_t)(r.meta >> 52);
-    for (uint32_t j = 0; j < len; j++)
-      o[j] = (uint8_t)(r.pat >> ((j % period) * 8));
+  // tiles: a record's offset is the prefix sum of the lengths before it
+  for (const DevSeqTile& t : R.tiles) {
+    uint8_t* o = dec + t.dst0;
+    for (uint32_t k = 0; k < t.n_rec; k++) {
+      const DevSeq& r = R.seqs[t.rec0 + k];
+      const uint32_t lit = (uint32_t)(r.a >> 40) & 0x1ff;
+      const uint32_t ml = (uint32_t)(r.a >> 49) & 0x1ff;
+      const uint32_t period = (uint32_t)(r.a >> 58);
+      std::memcpy(o, raw + (r.a & ((1ull << 40) - 1)), lit);
+      o += lit;
+      for (uint32_t j = 0; j < ml; j++)
+        o[j] = (uint8_t)(r.pat >> ((j % period) * 8));
+      o += ml;
+    }
   }
+  for (const DevLit& L : R.lits_wave)
+    std::memcpy(dec + L.b, raw + (L.a & ((1ull << 40) - 1)), L.a >> 40);
   for (const auto* recs : {&R.res_lane, &R.res_wave})
     for (const DevBrRes& rec : *recs) {
       uint32_t pat_off = 0;
@@ -4128,14 +4203,24 @@ void check_decomp_bounds(const DecompRecs& R, uint64_t raw_len,
   };
   for (const DevSeg& s : R.segs)
     need(s.src_off + s.comp_len <= raw_len && s.dst_off + s.out_len <= img_len);
-  for (const auto* lits : {&R.lits_lane, &R.lits_wave})
-    for (const DevLit& L : *lits)
-      need((L.a & ((1ull << 40) - 1)) + (L.a >> 40) <= raw_len &&
-           L.b + (L.a >> 40) <= img_len);
-  for (const DevBrInl& r : R.brinl) {
-    uint64_t period = r.meta >> 52;
-    need(period >= 1 && period <= 8 &&
-         (r.meta & ((1ull << 40) - 1)) + ((r.meta >> 40) & 0xfff) <= img_len);
+  for (const DevLit& L : R.lits_wave)
+    need((L.a & ((1ull << 40) - 1)) + (L.a >> 40) <= raw_len &&
+         L.b + (L.a >> 40) <= img_len);
+  for (const DevSeqTile& t : R.tiles) {
+    need(t.n_rec >= 1 && t.n_rec <= SEQ_TILE_RECS &&
+         t.out_len <= SEQ_TILE_BYTES && t.rec0 + t.n_rec <= R.seqs.size() &&
+         t.dst0 + t.out_len <= img_len);
+    uint64_t sum = 0;
+    for (uint32_t k = 0; k < t.n_rec; k++) {
+      const DevSeq& r = R.seqs[t.rec0 + k];
+      const uint64_t lit = (r.a >> 40) & 0x1ff, ml = (r.a >> 49) & 0x1ff;
+      const uint64_t period = r.a >> 58;
+      need(lit <= 256 && ml <= 256 &&
+           (r.a & ((1ull << 40) - 1)) + lit <= raw_len &&
+           (ml == 0 || (period >= 1 && period <= 8)));
+      sum += lit + ml;
+    }
+    need(sum == t.out_len);
   }
   for (const auto* recs : {&R.res_lane, &R.res_wave})
     for (const DevBrRes& r : *recs) {
@@ -4278,9 +4363,8 @@ extern "C" int32_t gpuq_test_decompress(
   DecompDev D{
       d_raw, d_dec,
       B.upload(R.segs), (int)R.segs.size(),
-      B.upload(R.lits_lane), (int64_t)R.lits_lane.size(),
+      B.upload(R.seqs), B.upload(R.tiles), (int)R.tiles.size(),
       B.upload(R.lits_wave), (int)R.lits_wave.size(),
-      B.upload(R.brinl), (int64_t)R.brinl.size(),
       B.upload(R.res_lane), (int64_t)R.res_lane.size(),
       B.upload(R.res_wave), (int)R.res_wave.size(),
       B.upload(R.piece_pool), B.upload(R.brs),

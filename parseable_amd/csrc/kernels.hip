@@ -234,20 +234,6 @@ __global__ void k_brres_lane(uint8_t* __restrict__ dec,
     pat_off += pc.len;
   }
 }
-// inlined-pattern resolved matches: pure writes (records are dst-sorted,
-// adjacent lanes write adjacent regions)
-__global__ void k_brres_inl(uint8_t* __restrict__ dec,
-                            const DevBrInl* __restrict__ recs, int64_t n) {
-  int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= n) return;
-  const DevBrInl R = recs[r];
-  const uint64_t dst = R.meta & ((1ull << 40) - 1);
-  const uint32_t len = (uint32_t)(R.meta >> 40) & 0xfff;
-  const uint32_t period = (uint32_t)(R.meta >> 52);
-  uint8_t* o = dec + dst;
-  for (uint32_t j = 0; j < len; j++)
-    o[j] = (uint8_t)(R.pat >> ((j % period) * 8));
-}
 __global__ void __launch_bounds__(WAVE)
 k_brres_wave(uint8_t* __restrict__ dec, const DevBrRes* __restrict__ recs,
              const DevPiece* __restrict__ pieces, int n) {
@@ -266,26 +252,71 @@ k_brres_wave(uint8_t* __restrict__ dec, const DevBrRes* __restrict__ recs,
   }
 }
 
-// litpar literal copies: one record per sequence's literal run (host walk,
-// meta.cpp lz4_walk litpar mode). Records are independent; short runs get a
-// lane each (records are dst-sorted, so adjacent lanes touch adjacent
-// memory), long runs a wave.
-__global__ void k_lit_lane(const uint8_t* __restrict__ raw,
-                           uint8_t* __restrict__ dec,
-                           const DevLit* __restrict__ lits, int64_t n) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const DevLit L = lits[i];
-  const uint8_t* s = raw + (L.a & ((1ull << 40) - 1));
-  const uint32_t len = (uint32_t)(L.a >> 40);
-  uint8_t* o = dec + L.b;
-  uint32_t k = 0;
-  for (; k + 8 <= len; k += 8) {
-    uint64_t w;
-    __builtin_memcpy(&w, s + k, 8);
-    __builtin_memcpy(o + k, &w, 8);
+// litpar sequence tiles (host walk, meta.cpp lz4_walk litpar mode, merged
+// into DevSeq records by plan_decomp_page): one tile per block, one record
+// per thread. A record has no dst — its offset in the tile is the prefix
+// sum of the lengths before it — so the block assembles the tile's whole
+// output span in LDS and flushes it with aligned 16 B stores. The stage is
+// shifted by the destination's misalignment, which keeps the LDS side of
+// the flush body 16 B-aligned too. Only [dst0, dst0 + out_len) is written.
+__global__ void __launch_bounds__(SEQ_TILE_RECS)
+k_seq_tile(const uint8_t* __restrict__ raw, uint8_t* __restrict__ dec,
+           const DevSeq* __restrict__ seqs,
+           const DevSeqTile* __restrict__ tiles, int n) {
+  __shared__ __attribute__((aligned(16))) uint8_t stage[SEQ_TILE_BYTES + 16];
+  __shared__ uint32_t wtot[SEQ_TILE_RECS / WAVE];
+  if (blockIdx.x >= (unsigned)n) return;
+  const DevSeqTile T = tiles[blockIdx.x];
+  const uint32_t t = threadIdx.x, lane = t & (WAVE - 1);
+  const uint32_t out_len = min(T.out_len, SEQ_TILE_BYTES);
+  uint8_t* o = dec + T.dst0;
+  const uint32_t pad = (uint32_t)((uintptr_t)o & 15);
+
+  DevSeq R{0, 0};
+  if (t < T.n_rec) R = seqs[T.rec0 + t];
+  const uint32_t lit = (uint32_t)(R.a >> 40) & 0x1ff;
+  const uint32_t ml = (uint32_t)(R.a >> 49) & 0x1ff;
+  const uint32_t period = (uint32_t)(R.a >> 58);
+  const uint32_t len = lit + ml;
+  // block exclusive scan: wave scan + the wave totals through LDS
+  uint32_t incl = len;
+#pragma unroll
+  for (int d = 1; d < WAVE; d <<= 1) {
+    uint32_t y = __shfl_up(incl, d, WAVE);
+    if (lane >= (uint32_t)d) incl += y;
   }
-  for (; k < len; k++) o[k] = s[k];
+  if (lane == WAVE - 1) wtot[t / WAVE] = incl;
+  __syncthreads();
+  uint32_t off = incl - len;
+  for (uint32_t w = 0; w < t / WAVE; w++) off += wtot[w];
+
+  // the host checked out_len == sum of the lengths; never leave the stage
+  if (off + len <= out_len) {
+    uint8_t* sp = stage + pad + off;
+    const uint8_t* s = raw + (R.a & ((1ull << 40) - 1));
+    for (uint32_t k = 0; k < lit; k += 8) {
+      uint64_t w;
+      __builtin_memcpy(&w, s + k, 8);   // tail over-read stays in raw's slack
+      const uint32_t m = min(8u, lit - k);
+      for (uint32_t j = 0; j < m; j++) sp[k + j] = (uint8_t)(w >> (j * 8));
+    }
+    sp += lit;
+    for (uint32_t j = 0, q = 0; j < ml; j++) {
+      sp[j] = (uint8_t)(R.pat >> (q * 8));
+      if (++q == period) q = 0;
+    }
+  }
+  __syncthreads();
+
+  // flush: bytewise head up to the first 16 B-aligned address, 16 B body,
+  // bytewise tail (stage index pad + i holds output byte i)
+  const uint32_t head = min((16u - pad) & 15u, out_len);
+  if (t < head) o[t] = stage[pad + t];
+  const uint32_t body = (out_len - head) & ~15u;
+  for (uint32_t i = t * 16u; i < body; i += SEQ_TILE_RECS * 16u)
+    *(uint4*)(o + head + i) = *(const uint4*)(stage + pad + head + i);
+  const uint32_t tl = head + body + t;
+  if (tl < out_len) o[tl] = stage[pad + tl];
 }
 __global__ void __launch_bounds__(WAVE)
 k_lit_wave(const uint8_t* __restrict__ raw, uint8_t* __restrict__ dec,
@@ -2681,9 +2712,9 @@ void launch_lz4_seg(hipStream_t st, const uint8_t* raw, uint8_t* dec,
                     const DevSeg* segs, int n, int32_t* d_err) {
   if (n) hipLaunchKernelGGL(k_lz4_seg, dim3(n), dim3(WAVE), 0, st, raw, dec, segs, n, d_err);
 }
-void launch_lit_lane(hipStream_t st, const uint8_t* raw, uint8_t* dec,
-                     const DevLit* lits, int64_t n) {
-  if (n) hipLaunchKernelGGL(k_lit_lane, dim3((int)((n + 255) / 256)), dim3(256), 0, st, raw, dec, lits, n);
+void launch_seq_tile(hipStream_t st, const uint8_t* raw, uint8_t* dec,
+                     const DevSeq* seqs, const DevSeqTile* tiles, int n) {
+  if (n) hipLaunchKernelGGL(k_seq_tile, dim3(n), dim3(SEQ_TILE_RECS), 0, st, raw, dec, seqs, tiles, n);
 }
 void launch_lit_wave(hipStream_t st, const uint8_t* raw, uint8_t* dec,
                      const DevLit* lits, int n) {
@@ -2696,10 +2727,6 @@ void launch_lz4_backrefs(hipStream_t st, uint8_t* dec, const DevBr* brs,
 void launch_brres_lane(hipStream_t st, uint8_t* dec, const DevBrRes* recs,
                        const DevPiece* pieces, int64_t n) {
   if (n) hipLaunchKernelGGL(k_brres_lane, dim3((int)((n + 255) / 256)), dim3(256), 0, st, dec, recs, pieces, n);
-}
-void launch_brres_inl(hipStream_t st, uint8_t* dec, const DevBrInl* recs,
-                      int64_t n) {
-  if (n) hipLaunchKernelGGL(k_brres_inl, dim3((int)((n + 255) / 256)), dim3(256), 0, st, dec, recs, n);
 }
 void launch_brres_wave(hipStream_t st, uint8_t* dec, const DevBrRes* recs,
                        const DevPiece* pieces, int n) {

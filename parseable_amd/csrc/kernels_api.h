@@ -6,16 +6,14 @@
 namespace gpuq {
 void launch_lz4_seg(hipStream_t, const uint8_t* raw, uint8_t* dec,
                     const DevSeg*, int n, int32_t* d_err);
-void launch_lit_lane(hipStream_t, const uint8_t* raw, uint8_t* dec,
-                     const DevLit* lits, int64_t n);
+void launch_seq_tile(hipStream_t, const uint8_t* raw, uint8_t* dec,
+                     const DevSeq* seqs, const DevSeqTile* tiles, int n);
 void launch_lit_wave(hipStream_t, const uint8_t* raw, uint8_t* dec,
                      const DevLit* lits, int n);
 void launch_lz4_backrefs(hipStream_t, uint8_t* dec, const DevBr*,
                          const DevPageBr*, int n);
 void launch_brres_lane(hipStream_t, uint8_t* dec, const DevBrRes*,
                        const DevPiece*, int64_t n);
-void launch_brres_inl(hipStream_t, uint8_t* dec, const DevBrInl* recs,
-                      int64_t n);
 void launch_brres_wave(hipStream_t, uint8_t* dec, const DevBrRes*,
                        const DevPiece*, int n);
 void launch_def_levels(hipStream_t, const uint8_t* dec, const DevPage*,
