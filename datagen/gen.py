@@ -133,7 +133,8 @@ def _c6_batch(rng, n, minute, cols):
     dict-encoded, `message` and `tag` overflow the 4 KiB dictionary limit
     into PLAIN pages; `latency` is a REQUIRED column; `sparse` is all-NULL in
     odd minutes and null-free in even ones; minute 0 carries one 40,000-byte
-    message (Error ... TIMEOUT); minute 1 carries, from its middle row on,
+    message (Error ... TIMEOUT); `f_f64` is a half-open-unit-interval double,
+    20 % NULL; minute 1 carries, from its middle row on,
     320 consecutive messages of 120-189 '=' plus a short suffix (none,
     Error, =error, TIMEOUT, x), about 51 KB of PLAIN-page bytes over 90 %
     '='."""
@@ -196,6 +197,10 @@ def _c6_batch(rng, n, minute, cols):
     else:
         cols["sparse"] = pa.array(
             [f"sp-{v}" for v in rng.integers(0, 40, n)], type=pa.string())
+    # drawn after every other column, so that those keep their values: a
+    # NULL-bearing f64 column (20 % NULL) that overflows the dictionary
+    f64 = rng.random(n)
+    cols["f_f64"] = pa.array(f64, type=pa.float64(), mask=rng.random(n) < 0.20)
     tbl = pa.table(cols)
     fields = [f.with_nullable(False) if f.name == "latency" else f
               for f in tbl.schema]

@@ -133,6 +133,29 @@ typedef struct {
   int32_t hi_exclusive;/* BETWEEN only */
 } gpuq_pred;
 
+/* WHERE tree over `preds`: the AND / OR groups of the filter builder
+ * (Conditions { operator, condition_config, groups },
+ * alerts/alert_structs.rs:195-203; get_filter_string joins a group's
+ * conditions and parenthesised nested groups with " AND " / " OR ",
+ * alerts/alerts_utils.rs:390-424).
+ *  - node 0 is the root and has parent = -1; every other node has
+ *    0 <= parent < own index, and its parent is an AND or an OR;
+ *  - `pred` indexes `preds` and is read for LEAF nodes only; every pred is
+ *    used by exactly one leaf;
+ *  - an AND or OR without a child is an error (the reference's "conditions
+ *    must have at least one condition or group"), as are more than 32 leaves
+ *    and an OR nesting depth above 4 after normalisation;
+ *  - normalisation: a child of its parent's kind is flattened into it, a
+ *    single-child group collapses, a non-AND root is wrapped in an AND. A
+ *    tree that normalises to a pure conjunction builds exactly the plan the
+ *    flat `preds` list builds.
+ * There is no NOT node (negation lives in the leaf ops), so the formula is
+ * monotone and SQL's three-valued logic under WHERE reduces to the leaf
+ * rule: a leaf is 0 on a NULL row (IS_NULL excepted) and the tree combines
+ * 0/1 bytes — a row is selected iff the tree over those bytes is 1. */
+typedef enum { GPUQ_NODE_LEAF = 0, GPUQ_NODE_AND, GPUQ_NODE_OR } gpuq_node_kind;
+typedef struct { int32_t kind; int32_t parent; int32_t pred; } gpuq_where_node;
+
 typedef enum {
   GPUQ_AGG_COUNT_STAR = 0, GPUQ_AGG_COUNT, GPUQ_AGG_SUM,
   GPUQ_AGG_MIN, GPUQ_AGG_MAX,
@@ -203,6 +226,32 @@ gpuq_plan* gpuq_plan_build_from_stream(gpuq_ctx*, const char* stream_dir,
     const char* const* group_by, int32_t n_group_by,
     const gpuq_agg* aggs, int32_t n_aggs, int64_t limit,
     int64_t* fast_count);
+
+/* gpuq_plan_build / gpuq_plan_build_from_stream with a WHERE tree over
+ * `preds` (gpuq_where_node above; Conditions, alerts/alert_structs.rs:195-203,
+ * joined as get_filter_string does, alerts/alerts_utils.rs:390-424).
+ * n_nodes == 0 means the AND of all preds — what the two entry points above
+ * pass. Pruning evaluates the tree: a file or row group goes away only when
+ * the root can match no row (an AND if any child cannot, an OR only if no
+ * child can). Only leaves that are conjuncts of the root on p_timestamp
+ * bound the manifest time window, and any leaf elsewhere in the tree keeps
+ * the plan off the manifest count fast path. A malformed tree is a
+ * plan-build error (NULL + gpuq_last_error). */
+gpuq_plan* gpuq_plan_build_where(gpuq_ctx*,
+    const gpuq_file* files, int32_t n_files,
+    const char* const* projection, int32_t n_projection,
+    const gpuq_pred* preds, int32_t n_preds,
+    const char* const* group_by, int32_t n_group_by,
+    const gpuq_agg* aggs, int32_t n_aggs,
+    int64_t limit,
+    const gpuq_where_node* nodes, int32_t n_nodes);
+gpuq_plan* gpuq_plan_build_from_stream_where(gpuq_ctx*, const char* stream_dir,
+    const char* const* projection, int32_t n_projection,
+    const gpuq_pred* preds, int32_t n_preds,
+    const char* const* group_by, int32_t n_group_by,
+    const gpuq_agg* aggs, int32_t n_aggs, int64_t limit,
+    int64_t* fast_count,
+    const gpuq_where_node* nodes, int32_t n_nodes);
 
 /* Independent output partitions, one per selected device (the byte-balanced
  * row-group shards of balanced_file_groups, stream_schema_provider.rs:146-165,
@@ -326,6 +375,21 @@ int32_t gpuq_test_decompress(gpuq_ctx*, const gpuq_decomp_page* pages,
                              uint8_t sentinel, uint8_t* out, uint64_t out_cap,
                              uint64_t* arena_len, uint64_t* guard_len,
                              gpuq_decomp_stats* stats, int32_t* d_err);
+
+/* Runs one of the two mask-combine kernels of the WHERE-tree path on
+ * caller-supplied byte arrays. op GPUQ_MASK_OR_RESET: a |= b, then b = 1
+ * (k_mask_or_reset); GPUQ_MASK_AND: a &= b, b unchanged (k_mask_and). Each
+ * array is copied to a device address with (address % 16) == its lead
+ * (0..15), inside a buffer filled with the sentinel 0xA5: out_a / out_b
+ * receive GPUQ_MASK_TEST_MARGIN + lead + n + GPUQ_MASK_TEST_MARGIN bytes,
+ * the data starting at offset GPUQ_MASK_TEST_MARGIN + lead. Returns 0, or
+ * -1 with the message in gpuq_last_error. */
+enum { GPUQ_MASK_OR_RESET = 0, GPUQ_MASK_AND = 1 };
+#define GPUQ_MASK_TEST_MARGIN 32
+#define GPUQ_MASK_TEST_SENTINEL 0xA5
+int32_t gpuq_test_mask_ops(gpuq_ctx*, int32_t op, const uint8_t* a,
+                           const uint8_t* b, int64_t n, int32_t a_lead,
+                           int32_t b_lead, uint8_t* out_a, uint8_t* out_b);
 
 #ifdef __cplusplus
 }

@@ -33,6 +33,11 @@ class GpuqPred(C.Structure):
     ]
 
 
+class GpuqWhereNode(C.Structure):
+    """One node of the WHERE tree over the preds (gpuq_where_node)."""
+    _fields_ = [("kind", C.c_int32), ("parent", C.c_int32), ("pred", C.c_int32)]
+
+
 class GpuqAgg(C.Structure):
     _fields_ = [("op", C.c_int32), ("column", C.c_char_p)]
 
@@ -87,6 +92,12 @@ OPS = {"eq": 0, "ne": 1, "lt": 2, "le": 3, "gt": 4, "ge": 5, "between": 6, "cont
 STR_OPS = ("contains", "icontains", "starts_with", "ends_with", "not_contains",
            "not_icontains", "not_starts_with", "not_ends_with")
 NULL_OPS = ("is_null", "is_not_null")
+# gpuq_node_kind, and the query-IR keys of the two group kinds
+NODE_KINDS = {"leaf": 0, "and": 1, "or": 2}
+# gpuq_test_mask_ops (test support): ops, margin and sentinel of include/gpuq.h
+MASK_OPS = {"or_reset": 0, "and": 1}
+MASK_TEST_MARGIN = 32
+MASK_TEST_SENTINEL = 0xA5
 AGGS = {"count_star": 0, "count": 1, "sum": 2, "min": 3, "max": 4,
         "count_distinct": 5}
 
@@ -127,6 +138,19 @@ def load():
         C.POINTER(C.c_char_p), C.c_int32,
         C.POINTER(GpuqAgg), C.c_int32,
         C.c_int64,
+    ]
+    # the *_where entry points: the same argument lists + (nodes, n_nodes)
+    lib.gpuq_plan_build_from_stream_where.restype = C.c_void_p
+    lib.gpuq_plan_build_from_stream_where.argtypes = (
+        lib.gpuq_plan_build_from_stream.argtypes
+        + [C.POINTER(GpuqWhereNode), C.c_int32])
+    lib.gpuq_plan_build_where.restype = C.c_void_p
+    lib.gpuq_plan_build_where.argtypes = (
+        lib.gpuq_plan_build.argtypes + [C.POINTER(GpuqWhereNode), C.c_int32])
+    lib.gpuq_test_mask_ops.restype = C.c_int32
+    lib.gpuq_test_mask_ops.argtypes = [
+        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+        C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
     ]
     lib.gpuq_plan_partition_count.restype = C.c_int32
     lib.gpuq_plan_partition_count.argtypes = [C.c_void_p]
@@ -189,3 +213,27 @@ def decompress_pages(pages, mode="auto", raw_lead=0, host=None, session=None,
         d["mode"] = DECOMP_PATHS[d["mode"]]
         st.append(d)
     return out.raw[:arena_len.value], st, guard_len.value, d_err.value
+
+
+def mask_ops(session, op, a, b, a_lead=0, b_lead=0):
+    """Test support: run k_mask_or_reset ("or_reset": a |= b, b = 1) or
+    k_mask_and ("and": a &= b) on two equally long byte strings placed at
+    device addresses with (address % 16) == lead. `session` is a gpuq_ctx
+    handle. Returns (out_a, out_b): the whole device buffers, MASK_TEST_MARGIN
+    sentinel bytes + lead sentinel bytes before the data and MASK_TEST_MARGIN
+    after it."""
+    lib = load()
+    a, b = bytes(a), bytes(b)
+    if len(a) != len(b):
+        raise ValueError("mask_ops: a and b differ in length")
+    n = len(a)
+    ba = C.create_string_buffer(a, max(n, 1))
+    bb = C.create_string_buffer(b, max(n, 1))
+    out_a = C.create_string_buffer(2 * MASK_TEST_MARGIN + a_lead + n)
+    out_b = C.create_string_buffer(2 * MASK_TEST_MARGIN + b_lead + n)
+    rc = lib.gpuq_test_mask_ops(session, MASK_OPS[op], C.addressof(ba),
+                                C.addressof(bb), n, a_lead, b_lead,
+                                C.addressof(out_a), C.addressof(out_b))
+    if rc != 0:
+        raise RuntimeError(lib.gpuq_last_error(session).decode(errors="replace"))
+    return out_a.raw, out_b.raw

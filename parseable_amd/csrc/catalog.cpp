@@ -1,5 +1,6 @@
 #include "catalog.h"
 #include "json.h"
+#include "where.h"
 
 #include <cstring>
 #include <ctime>
@@ -87,9 +88,11 @@ struct Bound {
 // derive the ts window from predicates on p_timestamp (the injected
 // `>= lo AND < hi` arrives as a hi-exclusive BETWEEN; explicit BETWEEN is
 // inclusive -> hi+1)
-Bound ts_window(const gpuq_pred* preds, int32_t n) {
+// — only leaves that are conjuncts of the WHERE root: a time leaf inside an
+// OR bounds nothing
+Bound ts_window(const gpuq_pred* preds, const std::vector<int>& root_leaves) {
   Bound b;
-  for (int32_t i = 0; i < n; i++) {
+  for (int i : root_leaves) {
     const auto& p = preds[i];
     if (!p.column || strcmp(p.column, "p_timestamp") != 0) continue;
     if (p.op == GPUQ_BETWEEN) {
@@ -156,7 +159,10 @@ bool stats_can_match(const JValue& stats, const gpuq_pred& p, int64_t lit_i,
 // a file is pruned when some predicate provably matches no row. NE, the
 // LIKE family (CONTAINS .. NOT_ENDS_WITH) and IS [NOT] NULL never prune
 // (the reference behaves the same); BETWEEN decomposes into its two bounds.
-bool file_pruned(const JValue& fe, const gpuq_pred* preds, int32_t n) {
+// With a WHERE tree "some predicate" becomes a tree evaluation (where_none):
+// an AND can match no row if any child cannot, an OR only if no child can.
+bool file_pruned(const JValue& fe, const gpuq_pred* preds,
+                 const WhereTree& tree) {
   const JValue* cols = fe.get("columns");
   if (!cols || cols->kind != JValue::ARR) return false;
   auto find_stats = [&](const char* name) -> const JValue* {
@@ -166,15 +172,15 @@ bool file_pruned(const JValue& fe, const gpuq_pred* preds, int32_t n) {
     }
     return nullptr;
   };
-  for (int32_t i = 0; i < n; i++) {
+  auto leaf_none = [&](int i) -> bool {
     const auto& p = preds[i];
-    if (p.op == GPUQ_NE || p.op == GPUQ_CONTAINS || !p.column) continue;
+    if (p.op == GPUQ_NE || p.op == GPUQ_CONTAINS || !p.column) return false;
     // the rest of the LIKE family and IS [NOT] NULL never prune on min/max
     // either (manifest stats carry no null counts; a null op's literal
     // fields are undefined and must not reach stats_can_match)
-    if (p.op >= GPUQ_ICONTAINS && p.op <= GPUQ_IS_NOT_NULL) continue;
+    if (p.op >= GPUQ_ICONTAINS && p.op <= GPUQ_IS_NOT_NULL) return false;
     const JValue* st = find_stats(p.column);
-    if (!st || st->kind != JValue::OBJ) continue;
+    if (!st || st->kind != JValue::OBJ) return false;
     if (p.op == GPUQ_BETWEEN) {
       gpuq_pred lo = p; lo.op = GPUQ_GE;  // x >= lo
       if (!stats_can_match(*st, lo, p.i64[0], p.f64[0], nullptr, GPUQ_GE)) return true;
@@ -183,15 +189,17 @@ bool file_pruned(const JValue& fe, const gpuq_pred* preds, int32_t n) {
     } else {
       if (!stats_can_match(*st, p, p.i64[0], p.f64[0], p.str, p.op)) return true;
     }
-  }
-  return false;
+    return false;
+  };
+  return where_none(tree, tree.root, leaf_none);
 }
 
 }  // namespace
 
 CatalogPlanInput catalog_plan(const std::string& stream_dir,
                               const gpuq_pred* preds, int32_t n_preds,
-                              bool bare_count_star) {
+                              bool bare_count_star,
+                              const gpuq_where_node* nodes, int32_t n_nodes) {
   CatalogPlanInput out;
   std::string root = stream_dir;
   size_t slash = root.find_last_of('/');
@@ -200,11 +208,14 @@ CatalogPlanInput catalog_plan(const std::string& stream_dir,
   JPtr snap_doc = JsonParser(read_file(stream_dir + "/stream.json")).parse();
   const JValue& snapshot = snap_doc->at("snapshot");
   const JValue& mlist = snapshot.at("manifest_list");
-  Bound win = ts_window(preds, n_preds);
+  const WhereTree tree = where_normalise(nodes, n_nodes, n_preds);
+  Bound win = ts_window(preds, tree.root_leaves);
 
   // value predicates excluding the window predicate itself (it is still a
   // pred for file-level ts pruning, so keep the full list for file_pruned)
-  bool has_value_preds = false;
+  // — and any leaf below an OR counts as one, time leaves included: the
+  // manifest sums cannot answer a disjunction
+  bool has_value_preds = !tree.conj;
   for (int32_t i = 0; i < n_preds; i++)
     if (!preds[i].column || strcmp(preds[i].column, "p_timestamp") != 0 ||
         preds[i].op == GPUQ_IS_NULL || preds[i].op == GPUQ_IS_NOT_NULL)
@@ -223,7 +234,7 @@ CatalogPlanInput catalog_plan(const std::string& stream_dir,
     if (!mpath.empty() && mpath[0] != '/') mpath = root + "/" + mpath;
     JPtr man = JsonParser(decode_manifest_text(read_file(mpath))).parse();
     for (const auto& fe : man->at("files").arr) {
-      if (file_pruned(*fe, preds, n_preds)) continue;
+      if (file_pruned(*fe, preds, tree)) continue;
       kept_files.push_back(fe);
     }
   }

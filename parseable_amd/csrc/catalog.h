@@ -20,9 +20,13 @@ struct CatalogPlanInput {
 };
 
 // preds: the full conjunction including the injected time range
-// (a hi-exclusive BETWEEN on p_timestamp). Throws on malformed metadata.
+// (a hi-exclusive BETWEEN on p_timestamp). nodes / n_nodes: the WHERE tree
+// over preds (where.h; n_nodes == 0 is the AND of all preds). Throws on
+// malformed metadata or a malformed tree.
 CatalogPlanInput catalog_plan(const std::string& stream_dir,
                               const gpuq_pred* preds, int32_t n_preds,
-                              bool bare_count_star);
+                              bool bare_count_star,
+                              const gpuq_where_node* nodes = nullptr,
+                              int32_t n_nodes = 0);
 
 }  // namespace gpuq

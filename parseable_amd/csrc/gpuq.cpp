@@ -11,6 +11,7 @@
 // Partial->Final merge left to the caller (one RCCL reduce across GPUs).
 #include "../../include/gpuq.h"
 #include "catalog.h"
+#include "where.h"
 #include "meta.h"
 #include "kernels_api.h"
 #include "dev_types.h"
@@ -24,6 +25,7 @@
 #include <algorithm>
 #include <array>
 #include <atomic>
+#include <functional>
 #include <cstring>
 #include <thread>
 #include <map>
@@ -184,6 +186,10 @@ struct ColPlan {
   std::vector<int> contains_preds; // LIKE-family preds (window path on PLAIN
                                    // byte_array pages)
   std::vector<int> null_preds;     // IS [NOT] NULL (def levels only)
+  // WHERE-tree mask contexts (gpuq_plan::ctxs) holding a LUT of this column,
+  // ascending: the column's LUT slot j serves context lut_ctxs[j]. {0} for
+  // a flat conjunction — one LUT, the AND of lut_preds
+  std::vector<int> lut_ctxs;
   bool need_rank = false;   // utf8 min/max: values decoded as dict sort-ranks
   bool is_bin = false;       // DATE_BIN pseudo-column (query/mod.rs:665-735)
   int bin_src = -1;          // source column index (p_timestamp)
@@ -229,7 +235,9 @@ struct ChunkTask {
   // dict-derived per-chunk aux (host-built)
   std::vector<int32_t> remap;      // local dict id -> gid
   std::vector<int64_t> dictv;      // local dict values (i64 / f64 bits)
-  std::vector<uint8_t> lut;        // combined pred LUT (AND of lut_preds)
+  std::vector<uint8_t> lut;        // combined pred LUT (AND of lut_preds);
+                                   // with a WHERE tree: slot 0 of lut_ctxs
+  std::vector<std::vector<uint8_t>> lut_x;  // LUT slots 1.. (ColPlan::lut_ctxs)
   bool has_plain_data_pages = false;
   // hash-mode (raw-byte utf8) extras:
   std::vector<int64_t> strof;      // dict entries: page-relative [len] offsets
@@ -254,6 +262,14 @@ enum TaskKind { TK_DICT_GID, TK_DICT_VAL, TK_PLAIN_VAL, TK_DELTA_VAL,
                 TK_DICT_MASK, TK_BYTES_CONTAINS, TK_POOL_VAL,
                 TK_IS_NULL, TK_IS_NOT_NULL,  // def levels of any encoding
                 TK_N };
+// A mask-writing task (TK_DICT_MASK, TK_BYTES_CONTAINS, TK_IS_[NOT_]NULL) of
+// a WHERE-tree context other than 0 carries the context above the kind, so
+// the (kind, col) task key of context 0 — every task of a flat conjunction —
+// is what it always was.
+constexpr int TK_CTX_SHIFT = 8;
+inline int tk_ctx(int kind, int ctx) { return kind | (ctx << TK_CTX_SHIFT); }
+inline int tk_kind(int key) { return key & ((1 << TK_CTX_SHIFT) - 1); }
+inline int tk_ctx_of(int key) { return key >> TK_CTX_SHIFT; }
 
 struct Partition {
   int device = -1;
@@ -267,6 +283,9 @@ struct Partition {
   std::vector<int32_t> remap_pool;
   std::vector<int64_t> dictv_pool;
   std::vector<uint8_t> lut_pool;
+  // LUT slots 1.. of the WHERE-tree contexts: pool j+1 has lut_pool's layout
+  // (a page's aux_lut addresses every slot), zero where a column has fewer
+  std::vector<std::vector<uint8_t>> lut_pool_x;
   // segment-parallel LZ4 (host structure walk, meta.cpp lz4_walk)
   std::vector<DevSeg> segs;
   std::vector<DevBr> brs;            // deep/serial pages only (windowed wave)
@@ -300,6 +319,8 @@ struct Partition {
   int64_t* d_dictv = nullptr;
   uint8_t* d_lut = nullptr;
   uint8_t* d_mask = nullptr;
+  // acc / tmp pairs of the non-folded OR groups, one pair per nesting level
+  std::vector<uint8_t*> d_wbufs;
   int32_t* d_err = nullptr;
   uint64_t* d_table = nullptr;
   uint64_t* d_fsum = nullptr;    // [n_fsum][n_groups][4] superacc limbs
@@ -429,6 +450,25 @@ struct gpuq_plan {
   // GPUQ_DISTINCT_FORCE_HASH is unset; the claimed-pair list holds
   // distinct_pair_cap keys (GPUQ_DISTINCT_PAIR_CAP lowers it)
   std::vector<int> distinct_aggs;
+  // WHERE tree (where.h). A pure conjunction leaves has_tree false and
+  // everything below empty: the flat plan, context 0 = d_mask alone.
+  //  - a context is one AND-evaluation unit writing one mask buffer: the
+  //    root AND (context 0, d_mask) and every term of a non-folded OR;
+  //  - pred_ctx[p]: the context leaf p evaluates in, -1 when its OR group
+  //    was folded into a single-column LUT (WFold);
+  //  - a WOr at nesting level L accumulates in d_wbufs[2L] and evaluates its
+  //    later terms in d_wbufs[2L+1].
+  bool has_tree = false;
+  WhereTree where;
+  std::vector<int> pred_ctx;
+  struct WOr { int node; int ctx; int level; std::vector<int> terms; };
+  struct WFold { int node; int ctx; int col; };
+  struct WCtx { std::vector<int> ors; };   // indices into wors
+  std::vector<WCtx> ctxs;
+  std::vector<WOr> wors;
+  std::vector<WFold> wfolds;
+  int n_wbufs = 0;
+  int ctx_of(int pidx) const { return has_tree ? pred_ctx[pidx] : 0; }
   uint64_t distinct_bitmap_bits = DISTINCT_BITMAP_BITS;
   uint64_t distinct_lds_bits = DISTINCT_LDS_BITS;  // GPUQ_DISTINCT_LDS_BITS
   uint32_t distinct_pair_cap = DISTINCT_PAIR_CAP;
@@ -526,39 +566,49 @@ NullState null_pred_state(int op, const ColumnChunkMeta& cm, bool optional) {
 // (stream_schema_provider.rs:1049-1137): prune when the predicate can match
 // NO value in [min,max]. The LIKE family never prunes; IS [NOT] NULL prunes
 // on the footer null_count alone (its literal fields are undefined).
+// One leaf: TRUE when no row of the row group can satisfy it.
+bool leaf_rg_none(const PredPlan& pp, const FileMeta& fm,
+                  const RowGroupMeta& rg) {
+  if (op_is_like(pp.p.op)) return false;
+  if (op_is_null(pp.p.op)) {
+    int ci = fm.col_index(pp.col);
+    return ci >= 0 && null_pred_state(pp.p.op, rg.chunks[ci],
+                                      fm.columns[ci].optional) == NULLP_UNSAT;
+  }
+  if (pp.p.lit_kind != GPUQ_LIT_I64) return false;
+  int ci = fm.col_index(pp.col);
+  if (ci < 0) return false;
+  const auto& cm = rg.chunks[ci];
+  if (!cm.has_i64_stats) return false;
+  int64_t mn = cm.stat_min, mx = cm.stat_max;
+  bool can_match = true;
+  switch (pp.p.op) {
+    case GPUQ_EQ: can_match = pp.p.i64[0] >= mn && pp.p.i64[0] <= mx; break;
+    case GPUQ_LT: can_match = mn < pp.p.i64[0]; break;
+    case GPUQ_LE: can_match = mn <= pp.p.i64[0]; break;
+    case GPUQ_GT: can_match = mx > pp.p.i64[0]; break;
+    case GPUQ_GE: can_match = mx >= pp.p.i64[0]; break;
+    case GPUQ_BETWEEN:
+      can_match = (pp.p.hi_exclusive ? mn < pp.p.i64[1] : mn <= pp.p.i64[1]) &&
+                  mx >= pp.p.i64[0];
+      break;
+    default: break;
+  }
+  return !can_match;
+}
+// The row group goes away when the WHERE root can match no row: any leaf of
+// a flat conjunction; with a tree an AND if any child cannot, an OR only if
+// no child can (where_none).
 bool rg_pruned_by_stats(const gpuq_plan& plan, const FileMeta& fm,
                         const RowGroupMeta& rg) {
-  for (const auto& pp : plan.preds) {
-    if (op_is_like(pp.p.op)) continue;
-    if (op_is_null(pp.p.op)) {
-      int ci = fm.col_index(pp.col);
-      if (ci >= 0 && null_pred_state(pp.p.op, rg.chunks[ci],
-                                     fm.columns[ci].optional) == NULLP_UNSAT)
-        return true;
-      continue;
-    }
-    if (pp.p.lit_kind != GPUQ_LIT_I64) continue;
-    int ci = fm.col_index(pp.col);
-    if (ci < 0) continue;
-    const auto& cm = rg.chunks[ci];
-    if (!cm.has_i64_stats) continue;
-    int64_t mn = cm.stat_min, mx = cm.stat_max;
-    bool can_match = true;
-    switch (pp.p.op) {
-      case GPUQ_EQ: can_match = pp.p.i64[0] >= mn && pp.p.i64[0] <= mx; break;
-      case GPUQ_LT: can_match = mn < pp.p.i64[0]; break;
-      case GPUQ_LE: can_match = mn <= pp.p.i64[0]; break;
-      case GPUQ_GT: can_match = mx > pp.p.i64[0]; break;
-      case GPUQ_GE: can_match = mx >= pp.p.i64[0]; break;
-      case GPUQ_BETWEEN:
-        can_match = (pp.p.hi_exclusive ? mn < pp.p.i64[1] : mn <= pp.p.i64[1]) &&
-                    mx >= pp.p.i64[0];
-        break;
-      default: break;
-    }
-    if (!can_match) return true;
+  if (!plan.has_tree) {
+    for (const auto& pp : plan.preds)
+      if (leaf_rg_none(pp, fm, rg)) return true;
+    return false;
   }
-  return false;
+  return where_none(plan.where, plan.where.root, [&](int pi) {
+    return leaf_rg_none(plan.preds[pi], fm, rg);
+  });
 }
 
 // Chunk-stats predicate elision: TRUE when the footer stats prove EVERY row
@@ -1078,7 +1128,19 @@ extern "C" gpuq_plan* gpuq_plan_build(
     const char* const* projection, int32_t n_projection,
     const gpuq_pred* preds, int32_t n_preds,
     const char* const* group_by, int32_t n_group_by,
-    const gpuq_agg* aggs, int32_t n_aggs, int64_t limit) try {
+    const gpuq_agg* aggs, int32_t n_aggs, int64_t limit) {
+  return gpuq_plan_build_where(ctx, files, n_files, projection, n_projection,
+                               preds, n_preds, group_by, n_group_by, aggs,
+                               n_aggs, limit, nullptr, 0);
+}
+
+extern "C" gpuq_plan* gpuq_plan_build_where(
+    gpuq_ctx* ctx, const gpuq_file* files, int32_t n_files,
+    const char* const* projection, int32_t n_projection,
+    const gpuq_pred* preds, int32_t n_preds,
+    const char* const* group_by, int32_t n_group_by,
+    const gpuq_agg* aggs, int32_t n_aggs, int64_t limit,
+    const gpuq_where_node* nodes, int32_t n_nodes) try {
   (void)projection; (void)n_projection;
   auto plan = std::make_unique<gpuq_plan>();
   plan->ctx = ctx;
@@ -1117,6 +1179,15 @@ extern "C" gpuq_plan* gpuq_plan_build(
     // a null op carries no literal: its lit_kind/str/i64/f64 are not read
     if (!op_is_null(pp.p.op) && preds[i].str) pp.str_lit = preds[i].str;
     plan->preds.push_back(std::move(pp));
+  }
+  // WHERE tree: validated always; kept only when it is not a pure
+  // conjunction, so such a tree builds exactly the flat plan
+  {
+    WhereTree wt = where_normalise(nodes, n_nodes, n_preds);
+    if (!wt.conj) {
+      plan->has_tree = true;
+      plan->where = std::move(wt);
+    }
   }
   for (int32_t i = 0; i < n_group_by; i++) {
     std::string g = group_by[i];
@@ -1352,6 +1423,10 @@ extern "C" gpuq_plan* gpuq_plan_build(
   std::vector<RgRef> selected;
   // per null predicate: row groups by NullState (plan debug line)
   std::map<size_t, std::array<int64_t, 3>> null_dbg;
+  // per leaf: row groups evaluated per row / proven by chunk stats (the
+  // WHERE-tree plan debug lines)
+  std::vector<std::array<int64_t, 2>> leaf_dbg(plan->preds.size(),
+                                               std::array<int64_t, 2>{0, 0});
   for (int32_t i = 0; i < n_files; i++) {
     const auto& mf = *plan->files[i];
     std::vector<int32_t> rg_list;
@@ -1407,6 +1482,34 @@ extern "C" gpuq_plan* gpuq_plan_build(
   // BEFORE the per-partition build so every partition routes consistently.
   // (LIKE alone stays on the contains-window path: it handles PLAIN pages
   // already and is much faster than per-row byte scans.) ---
+  // The same walk tells whether an OR group over one utf8 column can fold
+  // into that column's LUT (below): only a column without PLAIN pages can.
+  // or_col(node): the one utf8 column whose string ops are all the leaves
+  // below `node`, else -1.
+  std::function<int(int)> or_col = [&](int ni) -> int {
+    const WNode& n = plan->where.nodes[ni];
+    if (n.kind == GPUQ_NODE_LEAF) {
+      const auto& pp = plan->preds[n.pred];
+      if (op_is_null(pp.p.op)) return -1;
+      int ci = find_or_add_col(plan->cols, pp.col);
+      return plan->cols[ci].phys == PT_BYTE_ARRAY ? ci : -1;
+    }
+    int col = -2;
+    for (int k : n.kids) {
+      int kc = or_col(k);
+      if (kc < 0 || (col != -2 && kc != col)) return -1;
+      col = kc;
+    }
+    return col;
+  };
+  std::vector<uint8_t> fold_cand(plan->cols.size(), 0),
+      probe_hash(plan->cols.size(), 0), col_plain(plan->cols.size(), 0);
+  if (plan->has_tree)
+    for (size_t ni = 0; ni < plan->where.nodes.size(); ni++)
+      if (plan->where.nodes[ni].kind == GPUQ_NODE_OR) {
+        int ci = or_col((int)ni);
+        if (ci >= 0) fold_cand[ci] = 1;
+      }
   {
     struct Probe { int col; const MappedFile* mf; const ColumnChunkMeta* cm; int64_t rows; };
     std::vector<Probe> probes;
@@ -1416,7 +1519,8 @@ extern "C" gpuq_plan* gpuq_plan_build(
       bool non_like = false;
       for (int pidx : c.lut_preds)
         non_like |= !op_is_like(plan->preds[pidx].p.op);
-      if (!(c.need_gid || c.need_rank || non_like)) continue;
+      if (!(c.need_gid || c.need_rank || non_like || fold_cand[ci])) continue;
+      probe_hash[ci] = c.need_gid || c.need_rank || non_like;
       for (auto& r : selected) {
         const auto& mf = *plan->files[r.file_idx];
         int si = mf.meta.col_index(c.name);
@@ -1433,7 +1537,10 @@ extern "C" gpuq_plan* gpuq_plan_build(
         if (pi.type == PAGE_DATA && pi.encoding == ENC_PLAIN) plain[i] = 1;
     });
     for (size_t i = 0; i < probes.size(); i++)
-      if (plain[i]) plan->cols[probes[i].col].hash_mode = true;
+      if (plain[i]) {
+        col_plain[probes[i].col] = 1;
+        if (probe_hash[probes[i].col]) plan->cols[probes[i].col].hash_mode = true;
+      }
     for (size_t ci = 0; ci < plan->cols.size(); ci++) {
       auto& c = plan->cols[ci];
       if (!c.hash_mode) continue;
@@ -1453,6 +1560,92 @@ extern "C" gpuq_plan* gpuq_plan_build(
       if (!is_key) { c.need_gid = false; c.need_gid_valid = false; }
     }
   }
+
+  // --- WHERE tree -> mask contexts. Every term of an OR group becomes a
+  // context of its own (one mask buffer evaluation), except an OR group
+  // over a single LUT-only utf8 column: that one folds into the column's
+  // LUT in the parent's context — the tree is evaluated per dictionary
+  // entry at plan build and costs one TK_DICT_MASK task, no buffer, no
+  // combine pass (the IN-list shape, level = 'a' OR level = 'b'). ---
+  std::vector<char> or_path(plan->where.nodes.size(), 0);  // 'l' lut, 'm' mask
+  if (plan->has_tree) {
+    plan->pred_ctx.assign(plan->preds.size(), 0);
+    plan->ctxs.emplace_back();
+    std::function<void(int, char)> mark_folded = [&](int ni, char tag) {
+      const WNode& n = plan->where.nodes[ni];
+      if (n.kind == GPUQ_NODE_LEAF) { plan->pred_ctx[n.pred] = -1; return; }
+      if (n.kind == GPUQ_NODE_OR) or_path[ni] = tag;
+      for (int k : n.kids) mark_folded(k, tag);
+    };
+    // ni: an AND group or a single leaf evaluated in context k, whose OR
+    // children sit at nesting level `level`
+    std::function<void(int, int, int)> assign = [&](int ni, int k, int level) {
+      const WNode& n = plan->where.nodes[ni];
+      if (n.kind == GPUQ_NODE_LEAF) { plan->pred_ctx[n.pred] = k; return; }
+      for (int kid : n.kids) {
+        const WNode& kn = plan->where.nodes[kid];
+        if (kn.kind == GPUQ_NODE_LEAF) { plan->pred_ctx[kn.pred] = k; continue; }
+        // normal form: the child of an AND is an OR
+        int fc = or_col(kid);
+        if (fc >= 0 && !plan->cols[fc].hash_mode && !col_plain[fc]) {
+          mark_folded(kid, 'l');
+          plan->wfolds.push_back({kid, k, fc});
+          continue;
+        }
+        or_path[kid] = 'm';
+        gpuq_plan::WOr wo;
+        wo.node = kid; wo.ctx = k; wo.level = level;
+        plan->n_wbufs = std::max(plan->n_wbufs, 2 * (level + 1));
+        for (int term : kn.kids) {
+          int k2 = (int)plan->ctxs.size();
+          plan->ctxs.emplace_back();
+          wo.terms.push_back(k2);
+          assign(term, k2, level + 1);
+        }
+        plan->wors.push_back(std::move(wo));
+        plan->ctxs[k].ors.push_back((int)plan->wors.size() - 1);
+      }
+    };
+    assign(plan->where.root, 0, 0);
+  }
+  // LUT slots per column: the contexts holding a LUT leaf or a folded group
+  for (size_t ci = 0; ci < plan->cols.size(); ci++) {
+    auto& c = plan->cols[ci];
+    if (c.lut_preds.empty()) continue;
+    if (!plan->has_tree) { c.lut_ctxs = {0}; continue; }
+    for (int pidx : c.lut_preds)
+      if (plan->pred_ctx[pidx] >= 0) c.lut_ctxs.push_back(plan->pred_ctx[pidx]);
+    for (auto& f : plan->wfolds)
+      if (f.col == (int)ci) c.lut_ctxs.push_back(f.ctx);
+    std::sort(c.lut_ctxs.begin(), c.lut_ctxs.end());
+    c.lut_ctxs.erase(std::unique(c.lut_ctxs.begin(), c.lut_ctxs.end()),
+                     c.lut_ctxs.end());
+  }
+  // one dictionary entry against the LUT of (column ci, context k): the AND
+  // of the context's leaves on the column and of its folded groups
+  std::function<bool(int, const uint8_t*, uint32_t)> eval_fold =
+      [&](int ni, const uint8_t* q, uint32_t l) -> bool {
+    const WNode& n = plan->where.nodes[ni];
+    if (n.kind == GPUQ_NODE_LEAF) {
+      const auto& pp = plan->preds[n.pred];
+      return eval_str_pred(pp.p, pp.str_lit, q, l);
+    }
+    for (int k : n.kids) {
+      bool v = eval_fold(k, q, l);
+      if (n.kind == GPUQ_NODE_OR ? v : !v) return v;
+    }
+    return n.kind == GPUQ_NODE_AND;
+  };
+  auto lut_entry = [&](int ci, int k, const uint8_t* q, uint32_t l) -> uint8_t {
+    for (int pidx : plan->cols[ci].lut_preds) {
+      if (plan->ctx_of(pidx) != k) continue;
+      const auto& pp = plan->preds[pidx];
+      if (!eval_str_pred(pp.p, pp.str_lit, q, l)) return 0;
+    }
+    for (auto& f : plan->wfolds)
+      if (f.col == ci && f.ctx == k && !eval_fold(f.node, q, l)) return 0;
+    return 1;
+  };
 
   // --- per-partition host build: page walks, dict processing, device
   // images. The 1 B-row configs have thousands of (row-group x column)
@@ -1488,7 +1681,9 @@ extern "C" gpuq_plan* gpuq_plan_build(
       uint64_t raw_off;
       uint32_t rstart;
       bool need_val_decode;
-      bool need_is_null, need_is_not_null;  // null preds the footer left open
+      // null preds the footer left open: (TK_IS_NULL | TK_IS_NOT_NULL,
+      // mask context), each once
+      std::vector<std::pair<int, int>> null_tasks;
     };
     std::vector<Stub> stubs;
     for (auto& r : part.rgs) {
@@ -1504,6 +1699,7 @@ extern "C" gpuq_plan* gpuq_plan_build(
           elided = pred_all_true(pp.p, rg.chunks[si],
                                  mf.meta.columns[si].optional);
         pred_eval[pi2] = !elided;
+        leaf_dbg[pi2][elided ? 1 : 0]++;
         if (op_is_null(pp.p.op))
           null_dbg[pi2][elided ? NULLP_PROVEN : NULLP_EVAL]++;
         if (!elided) {
@@ -1523,13 +1719,19 @@ extern "C" gpuq_plan* gpuq_plan_build(
         const auto& cm = rg.chunks[si];
         bool needs_val = c.val_always;
         for (int pidx : c.cmp_preds) needs_val |= pred_eval[pidx];
-        bool is_null = false, is_not_null = false;
+        std::vector<std::pair<int, int>> null_tasks;
         for (int pidx : c.null_preds) {
           if (!pred_eval[pidx]) continue;
-          (plan->preds[pidx].p.op == GPUQ_IS_NULL ? is_null : is_not_null) = true;
+          std::pair<int, int> nt{plan->preds[pidx].p.op == GPUQ_IS_NULL
+                                     ? TK_IS_NULL : TK_IS_NOT_NULL,
+                                 plan->ctx_of(pidx)};
+          if (std::find(null_tasks.begin(), null_tasks.end(), nt) ==
+              null_tasks.end())
+            null_tasks.push_back(nt);
         }
+        std::sort(null_tasks.begin(), null_tasks.end());
         stubs.push_back({r.file_idx, r.rg_idx, (int)ci, &cm, part.raw_bytes,
-                         r.row_start, needs_val, is_null, is_not_null});
+                         r.row_start, needs_val, std::move(null_tasks)});
         part.raw_bytes += cm.total_compressed_size;
         part.bytes_scanned += cm.total_compressed_size;
       }
@@ -1567,12 +1769,10 @@ extern "C" gpuq_plan* gpuq_plan_build(
             else if (c.need_gid || c.need_rank)
               dict_strs[i].emplace_back((const char*)q, l);
             if (!c.hash_mode && !c.lut_preds.empty()) {
-              uint8_t ok = 1;
-              for (int pidx : c.lut_preds) {
-                const auto& pp = plan->preds[pidx];
-                ok &= (uint8_t)eval_str_pred(pp.p, pp.str_lit, q, l);
-              }
-              t.lut.push_back(ok);
+              t.lut_x.resize(c.lut_ctxs.size() - 1);
+              for (size_t j = 0; j < c.lut_ctxs.size(); j++)
+                (j ? t.lut_x[j - 1] : t.lut)
+                    .push_back(lut_entry(s.col_idx, c.lut_ctxs[j], q, l));
             }
             q += l;
           }
@@ -1673,6 +1873,14 @@ extern "C" gpuq_plan* gpuq_plan_build(
       if (!c.hash_mode)
         part.dictv_pool.insert(part.dictv_pool.end(), t.dictv.begin(), t.dictv.end());
       part.lut_pool.insert(part.lut_pool.end(), t.lut.begin(), t.lut.end());
+      if (part.lut_pool_x.size() < t.lut_x.size())
+        part.lut_pool_x.resize(t.lut_x.size());
+      for (size_t j = 0; j < part.lut_pool_x.size(); j++) {
+        auto& px = part.lut_pool_x[j];
+        px.resize(bases[i].lut, 0);  // zero where earlier chunks had no slot
+        if (j < t.lut_x.size())
+          px.insert(px.end(), t.lut_x[j].begin(), t.lut_x[j].end());
+      }
       t.dec_base = part.dec_bytes;
       if (c.hash_mode) {
         // the dict page image joins the dec arena (device-side strings);
@@ -1719,6 +1927,7 @@ extern "C" gpuq_plan* gpuq_plan_build(
       }
     }
 
+    for (auto& px : part.lut_pool_x) px.resize(part.lut_pool.size(), 0);
     phase_mark("phase3 pools+cache");
 
     // phase 4 (parallel): per-chunk device images — DevPage descriptors,
@@ -1831,15 +2040,23 @@ extern "C" gpuq_plan* gpuq_plan_build(
         if (!c.lut_preds.empty() && !c.hash_mode) {
           // (hash-mode columns evaluate every predicate over row strrefs
           // with k_cmp_str at execute — no LUT/window tasks)
+          // one task per mask context with a LUT of this column (flat
+          // conjunction: context 0 alone)
           if (dict_enc) {
             dp.aux_lut = lut_base;
-            cb.tasks[{TK_DICT_MASK, t.col_idx}].push_back(this_pid);
+            for (int k : c.lut_ctxs)
+              cb.tasks[{tk_ctx(TK_DICT_MASK, k), t.col_idx}].push_back(this_pid);
           } else if (pi.encoding == ENC_PLAIN) {
             // PLAIN fallback page of a string column: the LIKE family only
-            // (an EQ..GE predicate would have put the column in hash mode)
+            // (an EQ..GE predicate would have put the column in hash mode,
+            // and an OR group folds only on a column without PLAIN pages)
             if ((int)c.contains_preds.size() != (int)c.lut_preds.size())
               throw std::runtime_error("non-LIKE predicate on PLAIN utf8 pages: next row");
-            cb.tasks[{TK_BYTES_CONTAINS, t.col_idx}].push_back(this_pid);
+            for (auto& f : plan->wfolds)
+              if (f.col == t.col_idx)
+                throw std::runtime_error("folded OR group on PLAIN utf8 pages");
+            for (int k : c.lut_ctxs)
+              cb.tasks[{tk_ctx(TK_BYTES_CONTAINS, k), t.col_idx}].push_back(this_pid);
             cb.citems.push_back({mf.data + pi.payload_off, pi.comp_size,
                                  pi.uncomp_size, this_pid, dp.dst_off,
                                  (uint32_t)pi.num_values, dp.optional != 0,
@@ -1848,10 +2065,8 @@ extern "C" gpuq_plan* gpuq_plan_build(
         }
         // IS [NOT] NULL reads the def levels alone: every data page of the
         // chunk, whatever its value encoding
-        if (stubs[ti].need_is_null)
-          cb.tasks[{TK_IS_NULL, t.col_idx}].push_back(this_pid);
-        if (stubs[ti].need_is_not_null)
-          cb.tasks[{TK_IS_NOT_NULL, t.col_idx}].push_back(this_pid);
+        for (auto& nt : stubs[ti].null_tasks)
+          cb.tasks[{tk_ctx(nt.first, nt.second), t.col_idx}].push_back(this_pid);
         cb.pages.push_back(dp);
       }
       if (row_in_rg != (uint32_t)mf.meta.row_groups[t.rg_idx].num_rows)
@@ -2061,7 +2276,11 @@ extern "C" gpuq_plan* gpuq_plan_build(
       std::map<int32_t, size_t> by_page;
       for (size_t i = 0; i < citems.size(); i++) by_page[citems[i].page_id] = i;
       for (auto& [key, ids] : part.tasks) {
-        if (key.first != TK_BYTES_CONTAINS) continue;
+        // the windows belong to the column: every context's task lists the
+        // same pages, the first one builds them
+        if (tk_kind(key.first) != TK_BYTES_CONTAINS ||
+            part.cwin_ranges.count(key.second))
+          continue;
         uint32_t off = (uint32_t)part.cwins.size();
         for (int32_t pid : ids) {
           const auto& L = locals[by_page.at(pid)];
@@ -2289,9 +2508,13 @@ extern "C" gpuq_plan* gpuq_plan_build(
           path = "hash";
         } else {
           bool lut = false, win = false;
+          int k = plan->ctx_of((int)pi);
+          if (k < 0)  // folded into the LUT of its OR group's context
+            for (auto& f : plan->wfolds)
+              if (f.col == ci) k = f.ctx;
           for (auto& part : plan->parts) {
-            lut |= part.tasks.count({TK_DICT_MASK, ci}) != 0;
-            win |= part.tasks.count({TK_BYTES_CONTAINS, ci}) != 0;
+            lut |= part.tasks.count({tk_ctx(TK_DICT_MASK, k), ci}) != 0;
+            win |= part.tasks.count({tk_ctx(TK_BYTES_CONTAINS, k), ci}) != 0;
           }
           path = lut && win ? "lut+window" : win ? "window" : lut ? "lut" : "pruned";
         }
@@ -2309,6 +2532,25 @@ extern "C" gpuq_plan* gpuq_plan_build(
                 pi, pp.col.c_str(), op_name(pp.p.op), path.c_str(),
                 (long long)n[0], (long long)n[1], (long long)n[2]);
       }
+    }
+    if (plan->has_tree) {
+      fprintf(stderr, "[gpuq plan] where %s contexts=%zu depth=%d\n",
+              where_expr(plan->where, plan->where.root).c_str(),
+              plan->ctxs.size(), plan->where.depth);
+      // per leaf: its mask context (-1: folded into a LUT) and how many row
+      // groups evaluate it per row — elision holds inside an OR as well
+      for (size_t pi = 0; pi < plan->preds.size(); pi++)
+        fprintf(stderr,
+                "[gpuq plan] where pred %zu col=%s op=%s ctx=%d rowgroups: "
+                "eval=%lld elided=%lld\n",
+                pi, plan->preds[pi].col.c_str(), op_name(plan->preds[pi].p.op),
+                plan->pred_ctx[pi], (long long)leaf_dbg[pi][0],
+                (long long)leaf_dbg[pi][1]);
+      for (size_t ni = 0; ni < plan->where.nodes.size(); ni++)
+        if (plan->where.nodes[ni].kind == GPUQ_NODE_OR)
+          fprintf(stderr, "[gpuq plan] or node=%zu terms=%zu path=%s\n", ni,
+                  plan->where.nodes[ni].kids.size(),
+                  or_path[ni] == 'l' ? "lut" : "mask");
     }
   }
   return plan.release();
@@ -2328,11 +2570,25 @@ extern "C" gpuq_plan* gpuq_plan_build_from_stream(
     const gpuq_pred* preds, int32_t n_preds,
     const char* const* group_by, int32_t n_group_by,
     const gpuq_agg* aggs, int32_t n_aggs, int64_t limit,
-    int64_t* fast_count) try {
+    int64_t* fast_count) {
+  return gpuq_plan_build_from_stream_where(
+      ctx, stream_dir, projection, n_projection, preds, n_preds, group_by,
+      n_group_by, aggs, n_aggs, limit, fast_count, nullptr, 0);
+}
+
+extern "C" gpuq_plan* gpuq_plan_build_from_stream_where(
+    gpuq_ctx* ctx, const char* stream_dir,
+    const char* const* projection, int32_t n_projection,
+    const gpuq_pred* preds, int32_t n_preds,
+    const char* const* group_by, int32_t n_group_by,
+    const gpuq_agg* aggs, int32_t n_aggs, int64_t limit,
+    int64_t* fast_count,
+    const gpuq_where_node* nodes, int32_t n_nodes) try {
   if (fast_count) *fast_count = -1;
   bool bare = (n_aggs == 1 && aggs && aggs[0].op == GPUQ_AGG_COUNT_STAR &&
                n_group_by == 0);
-  CatalogPlanInput in = catalog_plan(stream_dir, preds, n_preds, bare);
+  CatalogPlanInput in = catalog_plan(stream_dir, preds, n_preds, bare, nodes,
+                                     n_nodes);
   if (in.fast_count >= 0) {
     if (fast_count) *fast_count = in.fast_count;
     return nullptr;
@@ -2347,10 +2603,10 @@ extern "C" gpuq_plan* gpuq_plan_build_from_stream(
     files[i].row_groups = nullptr;
     files[i].n_row_groups = -1;
   }
-  gpuq_plan* plan = gpuq_plan_build(ctx, files.data(), (int32_t)files.size(),
-                                    projection, n_projection,
-                                    preds, n_preds, group_by, n_group_by,
-                                    aggs, n_aggs, limit);
+  gpuq_plan* plan = gpuq_plan_build_where(
+      ctx, files.data(), (int32_t)files.size(), projection, n_projection,
+      preds, n_preds, group_by, n_group_by, aggs, n_aggs, limit, nodes,
+      n_nodes);
   // footer null counts can drop every row group of every kept file (IS NULL
   // on a required column): the empty relation, like an all-pruned file list
   bool null_pred = false;
@@ -2433,7 +2689,15 @@ extern "C" int32_t gpuq_plan_load(gpuq_plan* plan, int32_t pi) try {
   };
   upload_pool(part.remap_pool.data(), part.remap_pool.size() * 4, (void**)&part.d_remap);
   upload_pool(part.dictv_pool.data(), part.dictv_pool.size() * 8, (void**)&part.d_dictv);
-  upload_pool(part.lut_pool.data(), part.lut_pool.size(), (void**)&part.d_lut);
+  if (part.lut_pool_x.empty()) {
+    upload_pool(part.lut_pool.data(), part.lut_pool.size(), (void**)&part.d_lut);
+  } else {
+    // WHERE-tree LUT slots: slot j at d_lut + j * lut_pool.size()
+    std::vector<uint8_t> all(part.lut_pool);
+    for (auto& px : part.lut_pool_x) all.insert(all.end(), px.begin(), px.end());
+    upload_pool(all.data(), all.size(), (void**)&part.d_lut);
+    HIP_TRY(hipStreamSynchronize(part.stream));  // `all` dies with this scope
+  }
   for (auto& kv : part.tasks) {
     int32_t* d = nullptr;
     upload_pool(kv.second.data(), kv.second.size() * 4, (void**)&d);
@@ -2470,6 +2734,10 @@ extern "C" int32_t gpuq_plan_load(gpuq_plan* plan, int32_t pi) try {
     }
   }
   HIP_TRY(hipMalloc(&part.d_mask, std::max<int64_t>(part.n_rows, 16)));
+  // acc / tmp pairs of the non-folded OR groups (none for a flat plan)
+  part.d_wbufs.assign(plan->n_wbufs, nullptr);
+  for (auto& wb : part.d_wbufs)
+    HIP_TRY(hipMalloc(&wb, std::max<int64_t>(part.n_rows, 16)));
   HIP_TRY(hipMalloc(&part.d_rowof, std::max<int64_t>(part.n_rows * 4, 16)));
   HIP_TRY(hipMalloc(&part.d_rank, std::max<int64_t>(part.n_rows * 4, 16)));
   HIP_TRY(hipMalloc(&part.d_scr, std::max<int64_t>(part.n_rows * 8, 16)));
@@ -3105,10 +3373,20 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
     HIP_TRY(hipEventRecord(ev1, st));
   } else {
   auto run_task = [&](const std::pair<const std::pair<int, int>,
-                                      std::vector<int32_t>>& kv) {
-    int kind = kv.first.first, col = kv.first.second;
+                                      std::vector<int32_t>>& kv,
+                      uint8_t* mk) {
+    // mk: the mask buffer of the task's WHERE context (d_mask for context
+    // 0); d_lut: that context's LUT slot of the column
+    const int kind = tk_kind(kv.first.first), kctx = tk_ctx_of(kv.first.first);
+    const int col = kv.first.second;
     int n = (int)kv.second.size();
     int32_t* ids = part.d_ids[kv.first];
+    const uint8_t* d_lut = part.d_lut;
+    if (kind == TK_DICT_MASK) {
+      const auto& lc = plan->cols[col].lut_ctxs;
+      d_lut += (size_t)(std::find(lc.begin(), lc.end(), kctx) - lc.begin()) *
+               part.lut_pool.size();
+    }
     // footer-proven null-free column: the direct decode alone, validity
     // asserted (mode 2) — the def-level pass, the scratch decode and the
     // expansion would each find nothing to do
@@ -3137,8 +3415,8 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
                            part.d_val[col], part.d_valid[col], nullptr, 2);
           return;
         case TK_DICT_MASK:
-          launch_dict_mask(st, part.d_dec, part.d_pages, ids, n, part.d_lut,
-                           part.d_mask, 2, part.d_err);
+          launch_dict_mask(st, part.d_dec, part.d_pages, ids, n, d_lut,
+                           mk, 2, part.d_err);
           return;
         default: break;  // delta has one launch already; contains needs rowof
       }
@@ -3208,35 +3486,36 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
         launch_def_levels(st, part.d_dec, part.d_pages, ids, n,
                           part.d_tmpvalid, nullptr, nullptr,
                           part.d_rank, part.d_present, part.d_err);
-        launch_dict_mask(st, part.d_dec, part.d_pages, ids, n, part.d_lut,
-                         part.d_mask, 0, part.d_err);
-        launch_dict_lut_scr(st, part.d_dec, part.d_pages, ids, n, part.d_lut,
+        launch_dict_mask(st, part.d_dec, part.d_pages, ids, n, d_lut,
+                         mk, 0, part.d_err);
+        launch_dict_lut_scr(st, part.d_dec, part.d_pages, ids, n, d_lut,
                             part.d_scr, part.d_present, part.d_err);
         launch_expand(st, part.d_dec, part.d_pages, ids, n, part.d_scr,
-                      part.d_rank, part.d_tmpvalid, part.d_mask, 2);
+                      part.d_rank, part.d_tmpvalid, mk, 2);
         break;
       case TK_BYTES_CONTAINS: {
         // def levels zero null rows in the mask and build the dense->row
         // map; the window kernel then has no serial work at all
         launch_def_levels(st, part.d_dec, part.d_pages, ids, n,
-                          part.d_tmpvalid, part.d_mask, part.d_rowof,
+                          part.d_tmpvalid, mk, part.d_rowof,
                           part.d_rank, part.d_present, part.d_err);
         auto rng = part.cwin_ranges.at(col);
         // one launch per LIKE-family pred, each with its own needle (mask &=)
         for (int pidx : plan->cols[col].contains_preds) {
+          if (plan->ctx_of(pidx) != kctx) continue;
           const std::string& lit = plan->preds[pidx].str_lit;
           launch_str_win(st, part.d_dec, part.d_cwins + rng.first,
                          (int)rng.second, part.d_pages, part.d_cstarts,
                          part.d_needle + part.needle_off[pidx],
                          (int)lit.size(), like_mode(plan->preds[pidx].p.op),
-                         part.d_rowof, part.d_mask);
+                         part.d_rowof, mk);
         }
         break;
       }
       case TK_IS_NOT_NULL:
         // the null_mask output clears NULL rows; all-valid pages return early
         launch_def_levels(st, part.d_dec, part.d_pages, ids, n,
-                          part.d_tmpvalid, part.d_mask, nullptr, nullptr,
+                          part.d_tmpvalid, mk, nullptr, nullptr,
                           part.d_present, part.d_err);
         break;
       case TK_IS_NULL:
@@ -3244,14 +3523,16 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
                           part.d_tmpvalid, nullptr, nullptr, nullptr,
                           part.d_present, part.d_err);
         launch_null_clear_valid(st, part.d_dec, part.d_pages, ids, n,
-                                part.d_tmpvalid, part.d_mask);
+                                part.d_tmpvalid, mk);
         break;
     }
   };
   for (auto& kv : part.tasks) {
     // the fused path aggregates this column where it decodes it (step 3)
     if (plan->fused_valagg && kv.first.second == plan->valagg_col) continue;
-    run_task(kv);
+    // mask tasks of the other WHERE contexts run with their OR group below
+    if (tk_ctx_of(kv.first.first) != 0) continue;
+    run_task(kv, part.d_mask);
   }
   // raw-byte utf8: device hash build assigns dense gids per hash-mode
   // group key (one shared table, rebuilt per column); string predicates
@@ -3297,10 +3578,15 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
       HIP_TRY(hipStreamSynchronize(st));
       part.hash_claimed[ci] = claimed;
     }
+  }
+  // string predicates of hash-mode columns and numeric comparisons of WHERE
+  // context k, over whole decoded columns, into the context's buffer mk
+  auto row_preds = [&](int k, uint8_t* mk) {
     for (size_t ci = 0; ci < plan->cols.size(); ci++) {
       auto& c = plan->cols[ci];
       if (!c.hash_mode || c.lut_preds.empty()) continue;
       for (int pidx : c.lut_preds) {
+        if (plan->ctx_of(pidx) != k) continue;
         const auto& pp = plan->preds[pidx];
         int op;
         switch (pp.p.op) {
@@ -3316,45 +3602,86 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
         launch_cmp_str(st, part.d_dec, part.d_val[(int)ci],
                        itv != part.d_valid.end() ? itv->second : nullptr,
                        part.d_needle + part.needle_off[pidx],
-                       (uint32_t)pp.str_lit.size(), op, part.d_mask,
+                       (uint32_t)pp.str_lit.size(), op, mk,
                        part.n_rows);
       }
     }
-  }
 
-  // i64 comparisons on decoded arrays
-  for (size_t ci = 0; ci < plan->cols.size(); ci++) {
-    auto& c = plan->cols[ci];
-    for (int pidx : c.cmp_preds) {
-      const auto& pp = plan->preds[pidx];
-      int mode;
-      switch (pp.p.op) {
-        case GPUQ_EQ: mode = CMP_EQ; break;
-        case GPUQ_NE: mode = CMP_NE; break;
-        case GPUQ_LT: mode = CMP_LT; break;
-        case GPUQ_LE: mode = CMP_LE; break;
-        case GPUQ_GT: mode = CMP_GT; break;
-        case GPUQ_GE: mode = CMP_GE; break;
-        case GPUQ_BETWEEN: mode = CMP_RANGE; break;
-        default: throw std::runtime_error("bad cmp op");
+    // i64 comparisons on decoded arrays
+    for (size_t ci = 0; ci < plan->cols.size(); ci++) {
+      auto& c = plan->cols[ci];
+      for (int pidx : c.cmp_preds) {
+        if (plan->ctx_of(pidx) != k) continue;
+        const auto& pp = plan->preds[pidx];
+        int mode;
+        switch (pp.p.op) {
+          case GPUQ_EQ: mode = CMP_EQ; break;
+          case GPUQ_NE: mode = CMP_NE; break;
+          case GPUQ_LT: mode = CMP_LT; break;
+          case GPUQ_LE: mode = CMP_LE; break;
+          case GPUQ_GT: mode = CMP_GT; break;
+          case GPUQ_GE: mode = CMP_GE; break;
+          case GPUQ_BETWEEN: mode = CMP_RANGE; break;
+          default: throw std::runtime_error("bad cmp op");
+        }
+        int is_f64 = (c.phys == PT_DOUBLE) ? 1 : 0;
+        int64_t lo = pp.p.i64[0], hi = pp.p.i64[1];
+        if (is_f64) {
+          memcpy(&lo, &pp.p.f64[0], 8);
+          memcpy(&hi, &pp.p.f64[1], 8);
+        }
+        // evaluate only over the row ranges the chunk stats could not prove
+        // (pred_all_true); proven rows keep their memset-1 mask
+        auto rit = part.pred_ranges.find(pidx);
+        if (rit == part.pred_ranges.end()) continue;
+        for (const auto& [row0, nrows] : rit->second)
+          launch_cmp_i64(st, part.d_val[(int)ci] + row0,
+                         part.d_valid[(int)ci] + row0,
+                         lo, hi, mode, pp.p.hi_exclusive, is_f64,
+                         mk + row0, nrows);
       }
-      int is_f64 = (c.phys == PT_DOUBLE) ? 1 : 0;
-      int64_t lo = pp.p.i64[0], hi = pp.p.i64[1];
-      if (is_f64) {
-        memcpy(&lo, &pp.p.f64[0], 8);
-        memcpy(&hi, &pp.p.f64[1], 8);
-      }
-      // evaluate only over the row ranges the chunk stats could not prove
-      // (pred_all_true); proven rows keep their memset-1 mask
-      auto rit = part.pred_ranges.find(pidx);
-      if (rit == part.pred_ranges.end()) continue;
-      for (const auto& [row0, nrows] : rit->second)
-        launch_cmp_i64(st, part.d_val[(int)ci] + row0,
-                       part.d_valid[(int)ci] + row0,
-                       lo, hi, mode, pp.p.hi_exclusive, is_f64,
-                       part.d_mask + row0, nrows);
     }
+  };
+  row_preds(0, part.d_mask);
+
+  // OR groups (WHERE tree): acc is set to 1 and the first term evaluates
+  // straight into it; every later term evaluates into tmp (all ones on
+  // entry) and k_mask_or_reset folds it in and re-arms tmp in one pass;
+  // k_mask_and folds acc into the parent's buffer. A term that is an AND
+  // group evaluates all its leaves into the one buffer; a nested OR recurses
+  // with the pair of the next level. d_mask is final after this block.
+  int where_combines = 0;
+  if (plan->has_tree && need_mask) {
+    for (size_t b = 1; b < part.d_wbufs.size(); b += 2)
+      HIP_TRY(hipMemsetAsync(part.d_wbufs[b], 1, part.n_rows, st));
+    std::function<void(int, uint8_t*)> eval_ors;
+    auto eval_ctx = [&](int k, uint8_t* mk) {
+      for (auto& kv : part.tasks)
+        if (tk_ctx_of(kv.first.first) == k) run_task(kv, mk);
+      row_preds(k, mk);
+      eval_ors(k, mk);
+    };
+    eval_ors = [&](int k, uint8_t* mk) {
+      for (int oi : plan->ctxs[k].ors) {
+        const auto& wo = plan->wors[oi];
+        uint8_t* acc = part.d_wbufs[2 * wo.level];
+        uint8_t* tmp = part.d_wbufs[2 * wo.level + 1];
+        HIP_TRY(hipMemsetAsync(acc, 1, part.n_rows, st));
+        eval_ctx(wo.terms[0], acc);
+        for (size_t t = 1; t < wo.terms.size(); t++) {
+          eval_ctx(wo.terms[t], tmp);
+          launch_mask_or_reset(st, acc, tmp, part.n_rows);
+          where_combines++;
+        }
+        launch_mask_and(st, mk, acc, part.n_rows);
+        where_combines++;
+      }
+    };
+    eval_ors(0, part.d_mask);
   }
+  if (plan->has_tree && plan->exec_dbg)
+    fprintf(stderr, "[gpuq exec] part %d: where bufs=%zu combines=%d\n", (int)pi,
+            part.d_wbufs.size(), where_combines);
 
   // 2b. DATE_BIN key materialization
   for (size_t ci = 0; ci < plan->cols.size(); ci++) {
@@ -3467,7 +3794,7 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
   } else {
     if (plan->fused_valagg)
       for (auto& kv : part.tasks)
-        if (kv.first.second == plan->valagg_col) run_task(kv);
+        if (kv.first.second == plan->valagg_col) run_task(kv, part.d_mask);
     launch_agg(st, a);
   }
   // 3b. COUNT(DISTINCT): one set pass per distinct agg over the same final
@@ -4082,6 +4409,7 @@ gpuq_plan::~gpuq_plan() {
     auto F = [](void* p) { if (p) (void)hipFree(p); };
     F(part.d_raw); F(part.d_dec); F(part.d_pages); F(part.d_remap);
     F(part.d_dictv); F(part.d_lut); F(part.d_mask); F(part.d_err);
+    for (auto* wb : part.d_wbufs) F(wb);
     F(part.d_table); F(part.d_fsum); F(part.d_agg_kind);
     F(part.d_hkeys); F(part.d_hgids); F(part.d_hcount); F(part.d_cgid);
     for (auto& kv : part.d_gid2ref) F(kv.second);
@@ -4376,6 +4704,59 @@ extern "C" int32_t gpuq_test_decompress(
   HIP_TRY(hipMemcpyAsync(&err, d_e, 4, hipMemcpyDeviceToHost, B.stream));
   HIP_TRY(hipStreamSynchronize(B.stream));
   if (d_err) *d_err = err;
+  return 0;
+} catch (const std::exception& e) {
+  if (ctx) ctx->set_error(e.what());
+  else g_null_ctx_error = e.what();
+  return -1;
+}
+
+// ------------------------------------------------------------------
+// test support: the WHERE-tree mask-combine kernels on caller-supplied bytes
+// (include/gpuq.h gpuq_test_mask_ops)
+// ------------------------------------------------------------------
+extern "C" int32_t gpuq_test_mask_ops(gpuq_ctx* ctx, int32_t op,
+                                      const uint8_t* a, const uint8_t* b,
+                                      int64_t n, int32_t a_lead,
+                                      int32_t b_lead, uint8_t* out_a,
+                                      uint8_t* out_b) try {
+  if (n < 0 || (n > 0 && (!a || !b)) || !out_a || !out_b || a_lead < 0 ||
+      a_lead > 15 || b_lead < 0 || b_lead > 15 ||
+      (op != GPUQ_MASK_OR_RESET && op != GPUQ_MASK_AND))
+    throw std::runtime_error("gpuq_test_mask_ops: bad argument");
+  if (!ctx || ctx->devices.empty())
+    throw std::runtime_error("gpuq_test_mask_ops: needs a session");
+  HIP_TRY(hipSetDevice(ctx->devices[0]));
+  struct Bufs {
+    uint8_t* d[2] = {nullptr, nullptr};
+    hipStream_t stream = nullptr;
+    ~Bufs() {
+      for (auto* p : d) if (p) (void)hipFree(p);
+      if (stream) (void)hipStreamDestroy(stream);
+    }
+  } B;
+  HIP_TRY(hipStreamCreateWithFlags(&B.stream, hipStreamNonBlocking));
+  // hipMalloc returns 256 B-aligned memory and the margin is a multiple of
+  // 16: the data lands at an address with (address % 16) == lead
+  const uint8_t* src[2] = {a, b};
+  const int32_t lead[2] = {a_lead, b_lead};
+  size_t len[2];
+  for (int i = 0; i < 2; i++) {
+    len[i] = 2 * (size_t)GPUQ_MASK_TEST_MARGIN + (size_t)lead[i] + (size_t)n;
+    HIP_TRY(hipMalloc(&B.d[i], len[i]));
+    HIP_TRY(hipMemsetAsync(B.d[i], GPUQ_MASK_TEST_SENTINEL, len[i], B.stream));
+    if (n)
+      HIP_TRY(hipMemcpyAsync(B.d[i] + GPUQ_MASK_TEST_MARGIN + lead[i], src[i],
+                             (size_t)n, hipMemcpyHostToDevice, B.stream));
+  }
+  uint8_t* da = B.d[0] + GPUQ_MASK_TEST_MARGIN + a_lead;
+  uint8_t* db = B.d[1] + GPUQ_MASK_TEST_MARGIN + b_lead;
+  if (op == GPUQ_MASK_OR_RESET) launch_mask_or_reset(B.stream, da, db, n);
+  else launch_mask_and(B.stream, da, db, n);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out_a, B.d[0], len[0], hipMemcpyDeviceToHost, B.stream));
+  HIP_TRY(hipMemcpyAsync(out_b, B.d[1], len[1], hipMemcpyDeviceToHost, B.stream));
+  HIP_TRY(hipStreamSynchronize(B.stream));
   return 0;
 } catch (const std::exception& e) {
   if (ctx) ctx->set_error(e.what());

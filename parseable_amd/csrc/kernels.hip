@@ -2706,6 +2706,71 @@ __global__ void k_init_table(uint64_t* table, int32_t n_groups, int n_aggs,
 }
 
 // ------------------------------------------------------------------
+// WHERE-tree mask combines (OR groups, gpuq.cpp eval_ors): pure streaming
+// passes over 1 B/row masks. k_mask_or_reset folds a finished term into the
+// OR accumulator and re-arms the term buffer in the same pass (a |= b;
+// b = 1: 2 B read + 2 B written per row); k_mask_and folds the accumulator
+// into the parent (a &= b: 2 B read + 1 B written). 16 B per lane per
+// access is the widest global access; the vector body starts at the first
+// 16 B-aligned address of the destination `a`, the head before it and the
+// tail after the last full vector go bytewise, so no byte outside [0, n) is
+// read or written. `b` may sit at any offset relative to `a`: its 16 B
+// accesses are byte-aligned copies, which gfx950's global path serves
+// unaligned.
+// ------------------------------------------------------------------
+constexpr int MASKOP_T = 256;
+template <bool OR_RESET>
+__device__ __forceinline__ void mask_combine(uint8_t* __restrict__ a,
+                                             uint8_t* __restrict__ b,
+                                             int64_t n) {
+  int64_t head = (int64_t)((16 - ((uintptr_t)a & 15)) & 15);
+  if (head > n) head = n;
+  const int64_t nvec = (n - head) >> 4;
+  const int64_t tail0 = head + (nvec << 4);
+  uint8_t* av = a + head;
+  uint8_t* bv = b + head;
+  const int64_t stride = (int64_t)gridDim.x * MASKOP_T;
+  for (int64_t v = (int64_t)blockIdx.x * MASKOP_T + threadIdx.x; v < nvec;
+       v += stride) {
+    uint4 x = *reinterpret_cast<const uint4*>(av + (v << 4));
+    uint4 y;
+    __builtin_memcpy(&y, bv + (v << 4), 16);
+    if (OR_RESET) {
+      x.x |= y.x; x.y |= y.y; x.z |= y.z; x.w |= y.w;
+      const uint4 ones = make_uint4(0x01010101u, 0x01010101u, 0x01010101u,
+                                    0x01010101u);
+      __builtin_memcpy(bv + (v << 4), &ones, 16);
+    } else {
+      x.x &= y.x; x.y &= y.y; x.z &= y.z; x.w &= y.w;
+    }
+    *reinterpret_cast<uint4*>(av + (v << 4)) = x;
+  }
+  // head + tail: at most 15 + 15 bytes, block 0 alone
+  if (blockIdx.x == 0) {
+    const int64_t nedge = head + (n - tail0);
+    for (int64_t e = threadIdx.x; e < nedge; e += MASKOP_T) {
+      const int64_t i = e < head ? e : tail0 + (e - head);
+      if (OR_RESET) {
+        a[i] |= b[i];
+        b[i] = 1;
+      } else {
+        a[i] &= b[i];
+      }
+    }
+  }
+}
+__global__ void __launch_bounds__(MASKOP_T)
+k_mask_or_reset(uint8_t* __restrict__ acc, uint8_t* __restrict__ tmp,
+                int64_t n) {
+  mask_combine<true>(acc, tmp, n);
+}
+__global__ void __launch_bounds__(MASKOP_T)
+k_mask_and(uint8_t* __restrict__ dst, const uint8_t* __restrict__ acc,
+           int64_t n) {
+  mask_combine<false>(dst, const_cast<uint8_t*>(acc), n);
+}
+
+// ------------------------------------------------------------------
 // host-side launchers (called from gpuq.cpp, same TU set)
 // ------------------------------------------------------------------
 void launch_lz4_seg(hipStream_t st, const uint8_t* raw, uint8_t* dec,
@@ -2817,6 +2882,23 @@ void launch_cmp_i64(hipStream_t st, const int64_t* col, const uint8_t* valid,
   int blocks = (int)((n + 255) / 256);
   if (blocks > 4096) blocks = 4096;
   if (n) hipLaunchKernelGGL(k_cmp_i64, dim3(blocks), dim3(256), 0, st, col, valid, lo, hi, mode, hi_excl, is_f64, mask, n);
+}
+// one 16 B vector per lane per trip; 2048 blocks (256 CUs x 8) cap the grid
+static int maskop_blocks(int64_t n) {
+  int64_t b = ((n >> 4) + MASKOP_T - 1) / MASKOP_T;
+  return b < 1 ? 1 : b > 2048 ? 2048 : (int)b;
+}
+void launch_mask_or_reset(hipStream_t st, uint8_t* acc, uint8_t* tmp,
+                          int64_t n) {
+  if (n > 0)
+    hipLaunchKernelGGL(k_mask_or_reset, dim3(maskop_blocks(n)), dim3(MASKOP_T),
+                       0, st, acc, tmp, n);
+}
+void launch_mask_and(hipStream_t st, uint8_t* dst, const uint8_t* acc,
+                     int64_t n) {
+  if (n > 0)
+    hipLaunchKernelGGL(k_mask_and, dim3(maskop_blocks(n)), dim3(MASKOP_T), 0,
+                       st, dst, acc, n);
 }
 void launch_compact(hipStream_t st, const uint8_t* mask, const int64_t* key_col,
                     int64_t n_rows, int64_t* out_keys, uint32_t* out_rows,

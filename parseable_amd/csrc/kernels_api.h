@@ -59,6 +59,11 @@ void launch_delta_i64(hipStream_t, const uint8_t* dec, const DevPage*,
 void launch_cmp_i64(hipStream_t, const int64_t* col, const uint8_t* valid,
                     int64_t lo, int64_t hi, int mode, int hi_excl, int is_f64,
                     uint8_t* mask, int64_t n);
+// WHERE-tree mask combines over n 0/1 bytes (any alignment, any relative
+// misalignment): acc |= tmp then tmp = 1 (k_mask_or_reset); dst &= acc
+// (k_mask_and)
+void launch_mask_or_reset(hipStream_t, uint8_t* acc, uint8_t* tmp, int64_t n);
+void launch_mask_and(hipStream_t, uint8_t* dst, const uint8_t* acc, int64_t n);
 void launch_bin_i64(hipStream_t, const int64_t* col, const uint8_t* valid,
                     int64_t origin, int64_t stride, int64_t min_idx,
                     int32_t nbins, int32_t* out, int64_t n);

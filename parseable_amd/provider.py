@@ -26,8 +26,8 @@ import json
 import os
 
 from . import _lib
-from ._lib import (AGGS, NULL_OPS, OPS, STR_OPS, GpuqAgg, GpuqFile, GpuqPred,
-                   GpuqMetrics)
+from ._lib import (AGGS, NODE_KINDS, NULL_OPS, OPS, STR_OPS, GpuqAgg, GpuqFile,
+                   GpuqMetrics, GpuqPred, GpuqWhereNode)
 
 
 class GpuqError(RuntimeError):
@@ -73,11 +73,87 @@ def _stats_entry(col):
     return col["stats"]
 
 
+def _group_kind(node):
+    """"and" / "or" for a WHERE group node ({"and": [...]} / {"or": [...]}),
+    None for a leaf pred dict."""
+    if "and" in node or "or" in node:
+        if len(node) != 1:
+            raise GpuqError("a where group has exactly one key, 'and' or 'or'")
+        return "and" if "and" in node else "or"
+    return None
+
+
+def where_leaves(node):
+    """Leaf pred dicts of a WHERE tree, depth first in list order — the order
+    _build_c_query numbers them in."""
+    kind = _group_kind(node)
+    if kind is None:
+        return [node]
+    return [leaf for kid in node[kind] for leaf in where_leaves(kid)]
+
+
+def _check_groups(node):
+    """A group without a child is an error wherever it sits — also inside a
+    conjunction that is flattened here and never reaches the library."""
+    kind = _group_kind(node)
+    if kind is None:
+        return
+    if not isinstance(node[kind], (list, tuple)) or not node[kind]:
+        raise GpuqError("where: conditions must have at least one "
+                        "condition or group")
+    for kid in node[kind]:
+        _check_groups(kid)
+
+
+def _where_is_conjunction(node):
+    """A tree of AND groups and leaves alone: the flat predicate list."""
+    kind = _group_kind(node)
+    if kind is None:
+        return True
+    return kind == "and" and all(_where_is_conjunction(k) for k in node[kind])
+
+
+def _query_filter(query):
+    """-> (flat, tree): `flat` are the conjuncts of the query's root AND that
+    are plain leaves — `preds`, plus the leaves of a `where` that is itself a
+    pure conjunction (such a query IS its flat form, in both planners) —
+    and `tree` the remaining `where` with an OR somewhere in it, or None.
+    The injected time range is not included."""
+    flat = list(query.get("preds", []))
+    where = query.get("where")
+    if where is None:
+        return flat, None
+    _check_groups(where)
+    if _where_is_conjunction(where):
+        return flat + where_leaves(where), None
+    return flat, where
+
+
+def _time_pred(tr):
+    return {"col": "p_timestamp", "op": "between",
+            "lo": tr[0], "hi": tr[1], "hi_exclusive": True}
+
+
+def _prune_tree(query):
+    """The whole filter as one tree for pruning: preds AND time range AND
+    where."""
+    flat, tree = _query_filter(query)
+    kids = list(flat)
+    if query.get("time_range"):
+        kids.append(_time_pred(query["time_range"]))
+    if tree is not None:
+        kids.append(tree)
+    return {"and": kids}
+
+
 def _file_pruned(file_entry, preds):
     """Port of ManifestExt::can_be_pruned (stream_schema_provider.rs:1049-1078):
     a file is pruned when some predicate provably matches no row. BETWEEN is
     decomposed into ge(lo) + le/lt(hi) bounds as the reference's injected
-    filters are (query/mod.rs:829-888)."""
+    filters are (query/mod.rs:829-888). `preds` is a list of conjuncts; a
+    conjunct may be a WHERE group ({"and": [...]} / {"or": [...]}): an AND
+    matches no row if any child cannot, an OR only if no child can (the
+    catalog.cpp planner evaluates the same tree)."""
     cols = {c["name"]: c for c in file_entry.get("columns", [])}
 
     def check(col, op, value):
@@ -113,18 +189,22 @@ def _file_pruned(file_entry, preds):
             return False
         return not sat
 
-    for p in preds:
+    def none(p):
+        kind = _group_kind(p)
+        if kind == "and":
+            return any(none(k) for k in p[kind])
+        if kind == "or":
+            return bool(p[kind]) and all(none(k) for k in p[kind])
         op = p["op"]
         col = p["col"]
         if op == "between":
-            if check(col, "ge", p["lo"]) or check(col, "le" if not p.get("hi_exclusive") else "lt", p["hi"]):
-                return True
-        elif op == "ne" or op in STR_OPS or op in NULL_OPS:
-            continue  # no literal to compare (null ops) / no min/max reasoning
-        else:
-            if check(col, op, p["lit"]):
-                return True
-    return False
+            return (check(col, "ge", p["lo"])
+                    or check(col, "le" if not p.get("hi_exclusive") else "lt", p["hi"]))
+        if op == "ne" or op in STR_OPS or op in NULL_OPS:
+            return False  # no literal to compare (null ops) / no min/max reasoning
+        return check(col, op, p["lit"])
+
+    return any(none(p) for p in preds)
 
 
 ZSTD_MAGIC = b"\x28\xb5\x2f\xfd"
@@ -189,6 +269,10 @@ def supports_filters_pushdown(preds):
     (INTEGRATION.md)."""
     out = []
     for p in preds:
+        if _group_kind(p) is not None:
+            # an AND / OR group is never answered by partition prefixes
+            out.append("inexact")
+            continue
         op = p["op"]
         if p.get("col") == "p_timestamp":
             lit = p.get("lit")
@@ -260,13 +344,25 @@ class StagingScanner:
         import pyarrow as pa
         import pyarrow.compute as pc
 
-        mask = pa.array([True] * tbl.num_rows)
         tr = query.get("time_range")
         preds = list(query.get("preds", []))
         if tr is not None:
             preds.append({"col": "p_timestamp", "op": "between",
                           "lo": tr[0], "hi": tr[1], "hi_exclusive": True})
-        for p in preds:
+        if query.get("where") is not None:
+            preds.append(query["where"])
+
+        def node_mask(p):
+            # WHERE groups combine their children's NULL-free leaf masks
+            kind = _group_kind(p)
+            if kind is not None:
+                if not p[kind]:
+                    raise GpuqError("where: conditions must have at least "
+                                    "one condition or group")
+                m = node_mask(p[kind][0])
+                for kid in p[kind][1:]:
+                    m = (pc.and_ if kind == "and" else pc.or_)(m, node_mask(kid))
+                return m
             col = tbl.column(p["col"])
             if pa.types.is_dictionary(col.type):
                 col = col.cast(col.type.value_type)
@@ -290,7 +386,11 @@ class StagingScanner:
                      "le": pc.less_equal, "gt": pc.greater,
                      "ge": pc.greater_equal}[op]
                 m = f(col, p["lit"])
-            mask = pc.and_(mask, pc.fill_null(m, False))
+            return pc.fill_null(m, False)
+
+        mask = pa.array([True] * tbl.num_rows)
+        for p in preds:
+            mask = pc.and_(mask, node_mask(p))
         return mask
 
     def partial_batch(self, query):
@@ -636,29 +736,23 @@ class StandardTableProvider:
                 return EmptyScanResult(query)
             return plan
 
-        preds = list(query.get("preds", []))
+        # the root AND's plain conjuncts, and the OR-bearing where tree
+        preds, tree = _query_filter(query)
         time_range = query.get("time_range")
         files = self._manifest_files(time_range)
 
-        # prune: time bounds as predicates on p_timestamp + value predicates
-        prune_preds = preds.copy()
-        if time_range:
-            prune_preds.append(
-                {
-                    "col": "p_timestamp",
-                    "op": "between",
-                    "lo": time_range[0],
-                    "hi": time_range[1],
-                    "hi_exclusive": True,
-                }
-            )
+        # prune: time bounds as predicates on p_timestamp + value predicates,
+        # evaluated as one tree (an OR prunes only if every term does)
+        prune_preds = _prune_tree(query)["and"]
         kept = [f for f in files if not _file_pruned(f, prune_preds)]
 
         # count fast path (exact only when no value preds and the time range
-        # either is absent or fully covers every kept file's ts bounds)
+        # either is absent or fully covers every kept file's ts bounds); a
+        # leaf anywhere below an OR keeps the query off it
         sel = query.get("select", [])
         if (
             not preds
+            and tree is None
             and not query.get("group_by")
             and not query.get("select_cols")
             and len(sel) == 1
@@ -696,14 +790,9 @@ class StandardTableProvider:
         the CPU leg; the manifest count fast path is SKIPPED because staging
         rows are not in any manifest yet."""
         scanner = StagingScanner(self.staging_dir)
-        preds = list(query.get("preds", []))
         time_range = query.get("time_range")
         files = self._manifest_files(time_range)
-        prune_preds = preds.copy()
-        if time_range:
-            prune_preds.append({"col": "p_timestamp", "op": "between",
-                                "lo": time_range[0], "hi": time_range[1],
-                                "hi_exclusive": True})
+        prune_preds = _prune_tree(query)["and"]
         kept = [f for f in files if not _file_pruned(f, prune_preds)]
         root = os.path.dirname(self.stream_dir)
         paths = []
@@ -721,14 +810,9 @@ class StandardTableProvider:
         no manifest stats (only footer stats prune them), and the count fast
         path is skipped — their row counts are in no manifest
         (stream_schema_provider.rs:672-689)."""
-        preds = list(query.get("preds", []))
         time_range = query.get("time_range")
         files = self._manifest_files(time_range)
-        prune_preds = preds.copy()
-        if time_range:
-            prune_preds.append({"col": "p_timestamp", "op": "between",
-                                "lo": time_range[0], "hi": time_range[1],
-                                "hi_exclusive": True})
+        prune_preds = _prune_tree(query)["and"]
         kept = [f for f in files if not _file_pruned(f, prune_preds)]
         root = os.path.dirname(self.stream_dir)
         paths = list(legacy_paths)
@@ -758,14 +842,60 @@ def _build_c_projection(query: dict, keep):
     return arr, len(cols), limit
 
 
+def _flatten_where(preds, tree):
+    """-> (all_preds, nodes): the C form of `preds AND tree`. Node 0 is the
+    root AND; the flat preds are its first leaf children (pred i = leaf i),
+    then the tree follows depth first, its leaves numbered after them.
+    nodes: [(kind, parent, pred)], parents before children."""
+    all_preds = list(preds)
+    nodes = [(NODE_KINDS["and"], -1, -1)]
+    for i in range(len(preds)):
+        nodes.append((NODE_KINDS["leaf"], 0, i))
+
+    def walk(node, parent):
+        kind = _group_kind(node)
+        if kind is None:
+            nodes.append((NODE_KINDS["leaf"], parent, len(all_preds)))
+            all_preds.append(node)
+            return
+        nodes.append((NODE_KINDS[kind], parent, -1))
+        me = len(nodes) - 1
+        for kid in node[kind]:
+            walk(kid, me)
+
+    walk(tree, 0)
+    return all_preds, nodes
+
+
+def _build_c_where(query: dict, keep):
+    """-> (cnodes or None, n_nodes) for the *_where entry points, numbered
+    against the pred order of _build_c_query. No OR anywhere: (None, 0), the
+    AND of all preds."""
+    flat, tree = _query_filter(query)
+    if tree is None:
+        return None, 0
+    if query.get("time_range"):
+        flat = flat + [_time_pred(query["time_range"])]
+    _, nodes = _flatten_where(flat, tree)
+    cnodes = (GpuqWhereNode * len(nodes))()
+    for i, (kind, parent, pred) in enumerate(nodes):
+        cnodes[i].kind, cnodes[i].parent, cnodes[i].pred = kind, parent, pred
+    keep.append(cnodes)
+    return cnodes, len(nodes)
+
+
 def _build_c_query(query: dict, keep):
     """query IR -> (cpreds, n_preds, cgroup, n_group, caggs, n_aggs).
-    `keep` collects byte strings that must outlive the C call."""
-    preds = list(query.get("preds", []))
+    `keep` collects byte strings that must outlive the C call. Pred order:
+    the root conjuncts (preds, conjunct leaves of where), the time range,
+    then the leaves of an OR-bearing where tree depth first."""
+    preds, tree = _query_filter(query)
     tr = query.get("time_range")
     if tr:
         preds.append({"col": "p_timestamp", "op": "between",
                       "lo": tr[0], "hi": tr[1], "hi_exclusive": True})
+    if tree is not None:
+        preds, _ = _flatten_where(preds, tree)
     cpreds = (GpuqPred * max(len(preds), 1))()
     for i, p in enumerate(preds):
         b = p["col"].encode()
@@ -829,15 +959,16 @@ class GpuExecutionPlan:
 
         cpreds, np_, cgroup, ng, caggs, na = _build_c_query(query, self._keep)
         cproj, nproj, limit = _build_c_projection(query, self._keep)
+        cnodes, nn = _build_c_where(query, self._keep)
         if stream_dir is not None:
             # native catalog planner (§8f row 1): manifest selection, pruning
             # and the count fast path run inside libgpuq (catalog.cpp)
             fc = C.c_int64(-1)
-            self._plan = lib.gpuq_plan_build_from_stream(
+            self._plan = lib.gpuq_plan_build_from_stream_where(
                 session._ctx, stream_dir.encode(),
                 cproj, nproj,
                 cpreds, np_, cgroup, ng, caggs, na,
-                C.c_int64(limit), C.byref(fc))
+                C.c_int64(limit), C.byref(fc), cnodes, nn)
             if not self._plan:
                 if fc.value >= 0:
                     self.fast_count = fc.value
@@ -855,7 +986,7 @@ class GpuExecutionPlan:
             files[i].path = pb
             files[i].row_groups = None
             files[i].n_row_groups = -1
-        self._plan = lib.gpuq_plan_build(
+        self._plan = lib.gpuq_plan_build_where(
             session._ctx,
             files, n,
             cproj, nproj,
@@ -863,12 +994,16 @@ class GpuExecutionPlan:
             cgroup, ng,
             caggs, na,
             C.c_int64(limit),
+            cnodes, nn,
         )
         if not self._plan:
             raise GpuqError(f"plan_build failed: {session._err()}")
         # footer null counts can drop every row group (is_null on a required
         # column): the empty relation, as the native planner reports it
-        if (any(p["op"] in NULL_OPS for p in query.get("preds", []))
+        leaves = list(query.get("preds", []))
+        if query.get("where") is not None:
+            leaves += where_leaves(query["where"])
+        if (any(p["op"] in NULL_OPS for p in leaves)
                 and self.metrics()["rows_scanned"] == 0):
             self.close()
             self.empty = True
