@@ -443,6 +443,9 @@ struct gpuq_plan {
   bool valagg_late = false;      // group count known only at execute (hash /
                                  // numeric key): the old kernels stay armed
   int valagg_blocks = 1024;      // persistent grid cap
+  // dictionary-index decoders (kernels_api.h serial_walk), read at plan build:
+  // GPUQ_DICT_WALK=serial forces the one-header-per-step walk
+  bool dict_serial = false;
   bool exec_dbg = false;         // GPUQ_PLAN_DEBUG at build: log the agg path
   // COUNT(DISTINCT) (read at plan build): aggs of that kind in agg order;
   // bitmap path when n_groups x padded value cardinality fits
@@ -2404,6 +2407,8 @@ extern "C" gpuq_plan* gpuq_plan_build_where(
   plan->exec_dbg = getenv("GPUQ_PLAN_DEBUG") != nullptr;
   if (const char* e = getenv("GPUQ_VALAGG_BLOCKS"))
     plan->valagg_blocks = std::max(1, atoi(e));
+  if (const char* e = getenv("GPUQ_DICT_WALK"))
+    plan->dict_serial = strcmp(e, "serial") == 0;
   // COUNT(DISTINCT) knobs. The bitmap stays below 2^31 bits so the emit
   // pass's u32 list cursor cannot wrap; the pair cap can only be lowered.
   if (const char* e = getenv("GPUQ_DISTINCT_BITMAP_BITS"))
@@ -3317,6 +3322,7 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
   HIP_TRY(hipSetDevice(part.device));
   hipStream_t st = part.stream;
   int64_t t0 = now_ns();
+  const bool dw = plan->dict_serial;  // serial_walk of the dict launches
 
   hipEvent_t ev0, ev1, ev_decomp;
   HIP_TRY(hipEventCreate(&ev0));
@@ -3382,6 +3388,12 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
     int n = (int)kv.second.size();
     int32_t* ids = part.d_ids[kv.first];
     const uint8_t* d_lut = part.d_lut;
+    if (plan->exec_dbg &&
+        (kind == TK_DICT_GID || kind == TK_DICT_VAL || kind == TK_DICT_MASK))
+      fprintf(stderr,
+              "[gpuq exec] part %d: dict decode col=%s pages=%d dict_walk=%s\n",
+              pi, plan->cols[col].name.c_str(), n,
+              dw ? "serial" : "scan");
     if (kind == TK_DICT_MASK) {
       const auto& lc = plan->cols[col].lut_ctxs;
       d_lut += (size_t)(std::find(lc.begin(), lc.end(), kctx) - lc.begin()) *
@@ -3397,13 +3409,13 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
           launch_dict_gid(st, part.d_dec, part.d_pages, ids, n, part.d_remap,
                           part.d_gid[col],
                           it != part.d_valid.end() ? it->second : nullptr,
-                          nullptr, 2, part.d_err);
+                          nullptr, 2, dw, part.d_err);
           return;
         }
         case TK_DICT_VAL:
           launch_dict_i64(st, part.d_dec, part.d_pages, ids, n, part.d_dictv,
                           part.d_val[col], part.d_valid[col], nullptr, 2,
-                          part.d_err);
+                          dw, part.d_err);
           return;
         case TK_PLAIN_VAL:
           launch_plain_fixed(st, part.d_dec, part.d_pages, ids, n,
@@ -3416,7 +3428,7 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
           return;
         case TK_DICT_MASK:
           launch_dict_mask(st, part.d_dec, part.d_pages, ids, n, d_lut,
-                           mk, 2, part.d_err);
+                           mk, 2, dw, part.d_err);
           return;
         default: break;  // delta has one launch already; contains needs rowof
       }
@@ -3430,10 +3442,10 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
         launch_dict_gid(st, part.d_dec, part.d_pages, ids, n, part.d_remap,
                         part.d_gid[col],
                         it != part.d_valid.end() ? it->second : nullptr,
-                        part.d_present, 0, part.d_err);
+                        part.d_present, 0, dw, part.d_err);
         launch_dict_gid(st, part.d_dec, part.d_pages, ids, n, part.d_remap,
                         (int32_t*)part.d_scr, nullptr, part.d_present, 1,
-                        part.d_err);
+                        dw, part.d_err);
         launch_expand(st, part.d_dec, part.d_pages, ids, n, part.d_scr,
                       part.d_rank, v, (uint8_t*)part.d_gid[col], 1);
         break;
@@ -3444,10 +3456,10 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
                           part.d_rank, part.d_present, part.d_err);
         launch_dict_i64(st, part.d_dec, part.d_pages, ids, n, part.d_dictv,
                         part.d_val[col], part.d_valid[col], part.d_present, 0,
-                        part.d_err);
+                        dw, part.d_err);
         launch_dict_i64(st, part.d_dec, part.d_pages, ids, n, part.d_dictv,
                         (int64_t*)part.d_scr, nullptr, part.d_present, 1,
-                        part.d_err);
+                        dw, part.d_err);
         launch_expand(st, part.d_dec, part.d_pages, ids, n, part.d_scr,
                       part.d_rank, part.d_valid[col],
                       (uint8_t*)part.d_val[col], 0);
@@ -3487,9 +3499,9 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
                           part.d_tmpvalid, nullptr, nullptr,
                           part.d_rank, part.d_present, part.d_err);
         launch_dict_mask(st, part.d_dec, part.d_pages, ids, n, d_lut,
-                         mk, 0, part.d_err);
+                         mk, 0, dw, part.d_err);
         launch_dict_lut_scr(st, part.d_dec, part.d_pages, ids, n, d_lut,
-                            part.d_scr, part.d_present, part.d_err);
+                            part.d_scr, part.d_present, dw, part.d_err);
         launch_expand(st, part.d_dec, part.d_pages, ids, n, part.d_scr,
                       part.d_rank, part.d_tmpvalid, mk, 2);
         break;
@@ -3784,13 +3796,15 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
   // and the old kernels run
   bool fused = plan->fused_valagg && n_groups_exec * 16 <= 64 * 1024;
   if (plan->fused_valagg && plan->exec_dbg)
-    fprintf(stderr, "[gpuq exec] part %d: valagg=%s n_groups=%lld\n", pi,
-            fused ? "fused" : "fallback", (long long)n_groups_exec);
+    fprintf(stderr,
+            "[gpuq exec] part %d: valagg=%s n_groups=%lld dict_walk=%s\n", pi,
+            fused ? "fused" : "fallback", (long long)n_groups_exec,
+            dw ? "serial" : "scan");
   if (fused) {
     launch_val_agg(st, part.d_dec, part.d_pages, part.d_valagg_ids,
                    (int)part.valagg_ids.size(), part.d_dictv, a.key_gid[0],
                    a.mask, part.d_table, (int32_t)n_groups_exec, a.n_aggs,
-                   plan->aggs[1].kind, plan->valagg_blocks, part.d_err);
+                   plan->aggs[1].kind, plan->valagg_blocks, dw, part.d_err);
   } else {
     if (plan->fused_valagg)
       for (auto& kv : part.tasks)

@@ -649,6 +649,15 @@ struct EmitGid {
     if (valid) valid[row] = 1;
   }
   __device__ void null_at(uint32_t row) const { out[row] = 0; if (valid) valid[row] = 0; }
+  // batched form (EmitBatch): a batch's remap gathers go out together, the
+  // stores follow
+  struct Pending { uint32_t row; int32_t g; bool on; };
+  __device__ Pending fetch(uint32_t row, uint32_t idx, bool live) const {
+    return Pending{row, remap[idx], live};  // idx in bounds also for !live
+  }
+  __device__ void apply(const Pending& p) const {
+    if (p.on) { out[p.row] = p.g; if (valid) valid[p.row] = 1; }
+  }
 };
 struct EmitDictI64 {
   const int64_t* dictv;
@@ -673,10 +682,28 @@ struct EmitDictMask {
 // page decodes direct without consulting the all_valid probe (which only
 // recognises a single RLE run); def_levels() still supplies the value-stream
 // offset. No k_def_levels / scratch / k_expand launches accompany it.
-// Workgroups carry DP_WAVES waves per page: every wave walks the (cheap,
-// lane-redundant) run headers, but runs are unpacked round-robin by wave —
-// at 1 B-row scale a page-per-wave launch was ~1.9k waves, far too few to
-// hide latency on the unpack loads.
+// Workgroups carry DP_WAVES waves per page: every wave walks the run
+// headers, but runs are unpacked round-robin by wave — at 1 B-row scale a
+// page-per-wave launch was ~1.9k waves, far too few to hide latency on the
+// unpack loads.
+//
+// Header walk. A header's address depends on the header before it
+// (p += groups * bw), so walking one header per step is a chain of
+// dependent global loads, each in a new cache line. Writers close a
+// bit-packed run at 63 groups (header byte 0x7F, 504 values), so pages are
+// long sequences of equal one-byte headers at a fixed stride. After a
+// bit-packed run of G <= 63 groups has been parsed the wave therefore
+// probes 64 positions at once: lane k loads the byte at p + k * (1 + G*bw),
+// only while k full runs of G groups still fit the values left and the run
+// lies inside the page. A candidate counts only if every lower lane's byte
+// is the same header (ballot, count of trailing ones): lane 0's position is
+// a true header, and if positions 0..k-1 are true headers of full G-group
+// runs then position k is a true header too — so the accepted prefix is
+// exact, and a data byte that looks like a header sits beyond the first
+// mismatch and is never accepted. The first unaccepted position (an RLE
+// run, another group count, a multi-byte varint, the clipped last run) goes
+// through the one-header parse, after which probing resumes. `serial`
+// (GPUQ_DICT_WALK=serial) switches the probing off.
 #define DP_WAVES 4
 // Emitters whose per-value work is a chain of dependent loads (packed index
 // -> gather) with no store between them can declare BATCH > 1: the unpack
@@ -687,7 +714,8 @@ template <class Emit> struct EmitBatch { static constexpr int N = 1; };
 template <class Emit>
 __device__ void dict_page_decode(const DevPage& pg, const uint8_t* payload, Emit emit,
                                  const uint32_t* __restrict__ present,
-                                 int32_t page_id, int mode, int32_t* d_error) {
+                                 int32_t page_id, int mode, int32_t* d_error,
+                                 bool serial) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int wave = threadIdx.x / WAVE;
   const uint8_t* def_start; uint32_t def_len; bool all_valid;
@@ -709,35 +737,56 @@ __device__ void dict_page_decode(const DevPage& pg, const uint8_t* payload, Emit
         emit(target(i), 0);
       return;
     }
-    // lane-redundant run-header walk; data movement parallel per run,
-    // runs striped across the block's waves
+    // data movement parallel per run, runs striped across the block's waves
     const uint8_t* p = vals;
+    const uint8_t* const page_end = payload + pg.uncomp_size;
     const uint32_t dict_n = pg.dict_n;
+    const uint32_t mask_v = (bw >= 32) ? 0xffffffffu : ((1u << bw) - 1);
     uint32_t v = 0;
     uint32_t rc = 0;
-    while (v < nv) {
-      // varint header (redundant on all lanes)
-      uint64_t hdr = 0; int sh = 0;
-      for (;;) {
-        uint8_t b = *p++;
-        hdr |= (uint64_t)(b & 0x7f) << sh;
-        if (!(b & 0x80)) break;
-        sh += 7;
-      }
-      if (hdr & 1) {
-        uint32_t groups = (uint32_t)(hdr >> 1);
-        // one VALUE per lane (adjacent lanes -> adjacent rows): the emit
-        // stores coalesce into full lines. The group-of-8-per-lane layout
-        // this replaces made every store instruction span 64 half-used
-        // lines (PMC: 2.6x write amplification); the redundant group-byte
-        // reads (8 lanes share a group) stay in L1/L2.
-        uint32_t run_vals = groups * 8;
-        if (run_vals > nv - v) run_vals = nv - v;
-        const uint32_t mask_v = (bw >= 32) ? 0xffffffffu : ((1u << bw) - 1);
-        auto unpack = [&](uint32_t i) -> uint32_t {
+    // one bit-packed run: run_vals values from bit 0 of q0, first row v0
+    auto packed_run = [&](const uint8_t* q0, uint32_t v0, uint32_t run_vals) {
+      // one VALUE per lane (adjacent lanes -> adjacent rows): the emit
+      // stores coalesce into full lines. The group-of-8-per-lane layout
+      // this replaces made every store instruction span 64 half-used
+      // lines (PMC: 2.6x write amplification); the redundant group-byte
+      // reads (8 lanes share a group) stay in L1/L2.
+      if constexpr (EmitBatch<Emit>::N > 1) {
+        constexpr int NB = EmitBatch<Emit>::N;
+        // branch-free: lanes past the run's end re-read its last value
+        // (in bounds) and are switched off only at apply, so the NB
+        // loads of each phase issue back to back. Value i starts at bit
+        // i*bw of the run (groups are contiguous); one unaligned 8 B
+        // load covers it for every bw <= 32.
+        for (uint32_t i0 = lane; i0 < run_vals; i0 += WAVE * NB) {
+          uint32_t ic[NB], idx[NB];
+          uint64_t acc[NB];
+#pragma unroll
+          for (int u = 0; u < NB; u++) {
+            uint32_t i = i0 + u * WAVE;
+            ic[u] = i < run_vals ? i : run_vals - 1;
+            __builtin_memcpy(&acc[u], q0 + (((size_t)ic[u] * bw) >> 3), 8);
+          }
+          bool bad = false;
+#pragma unroll
+          for (int u = 0; u < NB; u++) {
+            idx[u] = (uint32_t)(acc[u] >> ((ic[u] * (uint32_t)bw) & 7)) & mask_v;
+            if (idx[u] >= dict_n) { bad = true; idx[u] = 0; }
+          }
+          if (bad) atomicExch(d_error, ERR_DICT_RANGE);
+          typename Emit::Pending pend[NB];
+#pragma unroll
+          for (int u = 0; u < NB; u++)
+            pend[u] = emit.fetch(target(v0 + ic[u]), idx[u],
+                                 i0 + u * WAVE < run_vals);
+#pragma unroll
+          for (int u = 0; u < NB; u++) emit.apply(pend[u]);
+        }
+      } else {
+        for (uint32_t i = lane; i < run_vals; i += WAVE) {
           uint32_t g = i >> 3;
           int k = (int)(i & 7);
-          const uint8_t* q = p + (size_t)g * bw;
+          const uint8_t* q = q0 + (size_t)g * bw;
           // one unaligned 8B load replaces the byte loop: bits beyond the
           // group's bw bytes are never selected (k*bw+bw <= 64 => the used
           // window lies inside q[0..8)); arena padding covers the over-read
@@ -751,51 +800,55 @@ __device__ void dict_page_decode(const DevPage& pg, const uint8_t* payload, Emit
             __builtin_memcpy(&acc2, q + (k * bw) / 8, 8);
             idx = (uint32_t)(acc2 >> ((k * bw) % 8)) & mask_v;
           }
-          return idx;
-        };
-        if ((rc++ % DP_WAVES) == (uint32_t)wave) {
-          if constexpr (EmitBatch<Emit>::N > 1) {
-            constexpr int NB = EmitBatch<Emit>::N;
-            // branch-free: lanes past the run's end re-read its last value
-            // (in bounds) and are switched off only at apply, so the NB
-            // loads of each phase issue back to back. Value i starts at bit
-            // i*bw of the run (groups are contiguous); one unaligned 8 B
-            // load covers it for every bw <= 32.
-            for (uint32_t i0 = lane; i0 < run_vals; i0 += WAVE * NB) {
-              uint32_t ic[NB], idx[NB];
-              uint64_t acc[NB];
-#pragma unroll
-              for (int u = 0; u < NB; u++) {
-                uint32_t i = i0 + u * WAVE;
-                ic[u] = i < run_vals ? i : run_vals - 1;
-                __builtin_memcpy(&acc[u], p + (((size_t)ic[u] * bw) >> 3), 8);
-              }
-              bool bad = false;
-#pragma unroll
-              for (int u = 0; u < NB; u++) {
-                idx[u] = (uint32_t)(acc[u] >> ((ic[u] * (uint32_t)bw) & 7)) & mask_v;
-                if (idx[u] >= dict_n) { bad = true; idx[u] = 0; }
-              }
-              if (bad) atomicExch(d_error, ERR_DICT_RANGE);
-              typename Emit::Pending pend[NB];
-#pragma unroll
-              for (int u = 0; u < NB; u++)
-                pend[u] = emit.fetch(target(v + ic[u]), idx[u],
-                                     i0 + u * WAVE < run_vals);
-#pragma unroll
-              for (int u = 0; u < NB; u++) emit.apply(pend[u]);
-            }
-          } else {
-            for (uint32_t i = lane; i < run_vals; i += WAVE) {
-              uint32_t idx = unpack(i);
-              if (idx >= dict_n) { atomicExch(d_error, ERR_DICT_RANGE); idx = 0; }
-              emit(target(v + i), idx);
-            }
+          if (idx >= dict_n) { atomicExch(d_error, ERR_DICT_RANGE); idx = 0; }
+          emit(target(v0 + i), idx);
+        }
+      }
+    };
+    while (v < nv) {
+      // varint header (redundant on all lanes)
+      uint64_t hdr = 0; int sh = 0;
+      for (;;) {
+        uint8_t b = *p++;
+        hdr |= (uint64_t)(b & 0x7f) << sh;
+        if (!(b & 0x80)) break;
+        sh += 7;
+      }
+      if (hdr & 1) {
+        uint32_t groups = (uint32_t)(hdr >> 1);
+        uint32_t run_vals = groups * 8;
+        if (run_vals > nv - v) run_vals = nv - v;
+        if ((rc++ % DP_WAVES) == (uint32_t)wave) packed_run(p, v, run_vals);
+        p += (size_t)groups * bw;
+        v += run_vals;
+        if (!serial && groups - 1u < 63u) {
+          // one-byte header, G = 1..63 groups: probe the next 64 positions
+          // a run of the same shape would put a header at (see above). hb <
+          // 0x80, so a byte equal to it at a true header position is a whole
+          // one-byte varint with the same G: that is what lets the loop go
+          // on after 64 accepts, when lane 0 again sits on a true header.
+          const uint32_t gv = groups * 8;
+          const uint32_t stride = 1 + groups * (uint32_t)bw;
+          const uint8_t hb = (uint8_t)hdr;
+          for (;;) {
+            const uint32_t full = (nv - v) / gv;  // full runs the values left hold
+            const int64_t room = page_end - p;    // bytes left in the page
+            const bool ok = (uint32_t)lane < full &&
+                            (int64_t)(lane + 1) * stride <= room;
+            const uint8_t b = ok ? p[(size_t)lane * stride] : (uint8_t)0;
+            const uint64_t hit = __ballot(ok && b == hb);
+            const uint32_t na =
+                ~hit ? (uint32_t)__builtin_ctzll(~hit) : (uint32_t)WAVE;
+            // accepted run j: header at p + j*stride, first value v + j*gv
+            for (uint32_t j = ((uint32_t)wave + DP_WAVES - rc % DP_WAVES) % DP_WAVES;
+                 j < na; j += DP_WAVES)
+              packed_run(p + (size_t)j * stride + 1, v + j * gv, gv);
+            p += (size_t)na * stride;
+            v += na * gv;
+            rc += na;
+            if (na < (uint32_t)WAVE) break;
           }
         }
-        p += (size_t)groups * bw;
-        uint32_t add = groups * 8;
-        v += (add > nv - v) ? (nv - v) : add;
       } else {
         uint32_t cnt = (uint32_t)(hdr >> 1);
         uint32_t val = 0;
@@ -816,13 +869,14 @@ template <class Emit>
 __global__ void __launch_bounds__(WAVE * DP_WAVES)
 k_dict_pages(const uint8_t* __restrict__ dec, const DevPage* __restrict__ pages,
              const int32_t* __restrict__ ids, int n, Emit emit,
-             const uint32_t* present, int mode, int32_t* d_error) {
+             const uint32_t* present, int mode, int32_t* d_error, int serial) {
   int pi = blockIdx.x;
   if (pi >= n) return;
   DevPage pg = pages[ids[pi]];
   Emit e = emit;
   e.advance(pg);  // per-page aux pool offsets
-  dict_page_decode(pg, dec + pg.dst_off, e, present, ids[pi], mode, d_error);
+  dict_page_decode(pg, dec + pg.dst_off, e, present, ids[pi], mode, d_error,
+                   serial != 0);
 }
 
 // wrappers adding per-page aux advance
@@ -830,6 +884,8 @@ struct EmitGidP : EmitGid {
   const int32_t* pool;
   __device__ void advance(const DevPage& pg) { remap = pool + pg.aux; }
 };
+#define GID_BATCH 4
+template <> struct EmitBatch<EmitGidP> { static constexpr int N = GID_BATCH; };
 struct EmitDictI64P : EmitDictI64 {
   const int64_t* pool;
   __device__ void advance(const DevPage& pg) { dictv = pool + pg.aux_val; }
@@ -2625,7 +2681,7 @@ k_val_agg(const uint8_t* __restrict__ dec, const DevPage* __restrict__ pages,
           const int64_t* __restrict__ dictv_pool,
           const int32_t* __restrict__ gid, const uint8_t* __restrict__ mask,
           uint64_t* __restrict__ table, int32_t n_groups, int slots,
-          int32_t* d_error) {
+          int32_t* d_error, int serial) {
   extern __shared__ uint64_t lt[];   // n_groups x {count, value}
   const uint64_t vinit = K1 == AGGK_MIN_I64 ? (uint64_t)INT64_MAX
                          : K1 == AGGK_MAX_I64 ? (uint64_t)INT64_MIN : 0ull;
@@ -2668,7 +2724,7 @@ k_val_agg(const uint8_t* __restrict__ dec, const DevPage* __restrict__ pages,
     } else {
       EmitValAgg<K1, MASK> e{dictv_pool + pg.aux_val, gid, mask, lt};
       dict_page_decode(pg, payload, e, (const uint32_t*)nullptr, ids[pi], 2,
-                       d_error);
+                       d_error, serial != 0);
     }
   }
   __syncthreads();
@@ -2832,33 +2888,35 @@ void launch_def_levels(hipStream_t st, const uint8_t* dec, const DevPage* pages,
 void launch_dict_gid(hipStream_t st, const uint8_t* dec, const DevPage* pages,
                      const int32_t* ids, int n, const int32_t* remap_pool,
                      int32_t* out, uint8_t* valid, const uint32_t* present,
-                     int mode, int32_t* d_err) {
+                     int mode, bool serial_walk, int32_t* d_err) {
   if (!n) return;
   EmitGidP e{}; e.pool = remap_pool; e.out = out; e.valid = valid;
-  hipLaunchKernelGGL(k_dict_pages<EmitGidP>, dim3(n), dim3(WAVE * DP_WAVES), 0, st, dec, pages, ids, n, e, present, mode, d_err);
+  hipLaunchKernelGGL(k_dict_pages<EmitGidP>, dim3(n), dim3(WAVE * DP_WAVES), 0, st, dec, pages, ids, n, e, present, mode, d_err, (int)serial_walk);
 }
 void launch_dict_i64(hipStream_t st, const uint8_t* dec, const DevPage* pages,
                      const int32_t* ids, int n, const int64_t* dictv_pool,
                      int64_t* out, uint8_t* valid, const uint32_t* present,
-                     int mode, int32_t* d_err) {
+                     int mode, bool serial_walk, int32_t* d_err) {
   if (!n) return;
   EmitDictI64P e{}; e.pool = dictv_pool; e.out = out; e.valid = valid;
-  hipLaunchKernelGGL(k_dict_pages<EmitDictI64P>, dim3(n), dim3(WAVE * DP_WAVES), 0, st, dec, pages, ids, n, e, present, mode, d_err);
+  hipLaunchKernelGGL(k_dict_pages<EmitDictI64P>, dim3(n), dim3(WAVE * DP_WAVES), 0, st, dec, pages, ids, n, e, present, mode, d_err, (int)serial_walk);
 }
 void launch_dict_mask(hipStream_t st, const uint8_t* dec, const DevPage* pages,
                       const int32_t* ids, int n, const uint8_t* lut_pool,
-                      uint8_t* mask, int mode, int32_t* d_err) {
+                      uint8_t* mask, int mode, bool serial_walk,
+                      int32_t* d_err) {
   if (!n) return;
   EmitDictMaskP e{}; e.pool = lut_pool; e.mask = mask;
-  hipLaunchKernelGGL(k_dict_pages<EmitDictMaskP>, dim3(n), dim3(WAVE * DP_WAVES), 0, st, dec, pages, ids, n, e, (const uint32_t*)nullptr, mode, d_err);
+  hipLaunchKernelGGL(k_dict_pages<EmitDictMaskP>, dim3(n), dim3(WAVE * DP_WAVES), 0, st, dec, pages, ids, n, e, (const uint32_t*)nullptr, mode, d_err, (int)serial_walk);
 }
 void launch_dict_lut_scr(hipStream_t st, const uint8_t* dec,
                          const DevPage* pages, const int32_t* ids, int n,
                          const uint8_t* lut_pool, uint8_t* scr,
-                         const uint32_t* present, int32_t* d_err) {
+                         const uint32_t* present, bool serial_walk,
+                         int32_t* d_err) {
   if (!n) return;
   EmitLutD e{}; e.pool = lut_pool; e.scr = scr;
-  hipLaunchKernelGGL(k_dict_pages<EmitLutD>, dim3(n), dim3(WAVE * DP_WAVES), 0, st, dec, pages, ids, n, e, present, 1, d_err);
+  hipLaunchKernelGGL(k_dict_pages<EmitLutD>, dim3(n), dim3(WAVE * DP_WAVES), 0, st, dec, pages, ids, n, e, present, 1, d_err, (int)serial_walk);
 }
 void launch_plain_fixed(hipStream_t st, const uint8_t* dec, const DevPage* pages,
                         const int32_t* ids, int n, int64_t* out, uint8_t* valid,
@@ -2952,7 +3010,7 @@ void launch_val_agg(hipStream_t st, const uint8_t* dec, const DevPage* pages,
                     const int32_t* ids, int n, const int64_t* dictv_pool,
                     const int32_t* gid, const uint8_t* mask, uint64_t* table,
                     int32_t n_groups, int n_aggs, int kind, int max_blocks,
-                    int32_t* d_err) {
+                    bool serial_walk, int32_t* d_err) {
   if (!n) return;
   // even page counts per persistent block: with n just above the cap a
   // plain min(n, cap) grid leaves half the blocks one page short
@@ -2964,7 +3022,7 @@ void launch_val_agg(hipStream_t st, const uint8_t* dec, const DevPage* pages,
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(WAVE * DP_WAVES), lds, st, dec,
                        pages, ids, n, dictv_pool, gid, mask, table, n_groups,
-                       slots, d_err);
+                       slots, d_err, (int)serial_walk);
   };
   if (mask) {
     switch (kind) {

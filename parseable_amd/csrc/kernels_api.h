@@ -32,20 +32,23 @@ void launch_str_win(hipStream_t, const uint8_t* dec, const DevCWin* wins,
 void launch_null_clear_valid(hipStream_t, const uint8_t* dec, const DevPage*,
                              const int32_t* ids, int n, const uint8_t* valid,
                              uint8_t* mask);
+// serial_walk (the dictionary-index decoders): parse one RLE run header per
+// step instead of probing 64 positions at once (GPUQ_DICT_WALK=serial)
 void launch_dict_gid(hipStream_t, const uint8_t* dec, const DevPage*,
                      const int32_t* ids, int n, const int32_t* remap_pool,
                      int32_t* out, uint8_t* valid, const uint32_t* present,
-                     int mode, int32_t* d_err);
+                     int mode, bool serial_walk, int32_t* d_err);
 void launch_dict_i64(hipStream_t, const uint8_t* dec, const DevPage*,
                      const int32_t* ids, int n, const int64_t* dictv_pool,
                      int64_t* out, uint8_t* valid, const uint32_t* present,
-                     int mode, int32_t* d_err);
+                     int mode, bool serial_walk, int32_t* d_err);
 void launch_dict_mask(hipStream_t, const uint8_t* dec, const DevPage*,
                       const int32_t* ids, int n, const uint8_t* lut_pool,
-                      uint8_t* mask, int mode, int32_t* d_err);
+                      uint8_t* mask, int mode, bool serial_walk, int32_t* d_err);
 void launch_dict_lut_scr(hipStream_t, const uint8_t* dec, const DevPage*,
                          const int32_t* ids, int n, const uint8_t* lut_pool,
-                         uint8_t* scr, const uint32_t* present, int32_t* d_err);
+                         uint8_t* scr, const uint32_t* present,
+                         bool serial_walk, int32_t* d_err);
 void launch_plain_fixed(hipStream_t, const uint8_t* dec, const DevPage*,
                         const int32_t* ids, int n, int64_t* out, uint8_t* valid,
                         const uint32_t* present, int mode, int32_t* d_err);
@@ -79,7 +82,7 @@ void launch_val_agg(hipStream_t, const uint8_t* dec, const DevPage*,
                     const int32_t* ids, int n, const int64_t* dictv_pool,
                     const int32_t* gid, const uint8_t* mask, uint64_t* table,
                     int32_t n_groups, int n_aggs, int kind, int max_blocks,
-                    int32_t* d_err);
+                    bool serial_walk, int32_t* d_err);
 void launch_agg(hipStream_t, const AggArgs&);
 void launch_pool_vals(hipStream_t, const uint8_t* dec, const DevPage*,
                       const int32_t* ids, int n, const int64_t* pool,
