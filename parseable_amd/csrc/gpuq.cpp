@@ -278,7 +278,6 @@ struct Partition {
   std::vector<ChunkTask> chunks;
   // host-built device images
   std::vector<DevPage> pages;                 // data pages only
-  std::vector<int32_t> ids[TK_N];             // per task kind... per column!
   std::map<std::pair<int,int>, std::vector<int32_t>> tasks;  // (kind,col)->page ids
   std::vector<int32_t> remap_pool;
   std::vector<int64_t> dictv_pool;
@@ -442,7 +441,8 @@ struct gpuq_plan {
   int valagg_col = -1;           // the aggregated column (index into cols)
   bool valagg_late = false;      // group count known only at execute (hash /
                                  // numeric key): the old kernels stay armed
-  int valagg_blocks = 1024;      // persistent grid cap
+  int valagg_blocks = 1024;      // persistent grid cap (GPUQ_VALAGG_BLOCKS)
+  bool no_fused_valagg = false;  // GPUQ_NO_FUSED_VALAGG
   // dictionary-index decoders (kernels_api.h serial_walk), read at plan build:
   // GPUQ_DICT_WALK=serial forces the one-header-per-step walk
   bool dict_serial = false;
@@ -515,6 +515,29 @@ extern "C" int32_t gpuq_device_count(void) {
 // plan building
 // ------------------------------------------------------------------
 namespace {
+
+// environment knobs, read once into the plan
+void read_env_knobs(gpuq_plan* plan) {
+  plan->exec_dbg = getenv("GPUQ_PLAN_DEBUG") != nullptr;
+  plan->no_fused_valagg = getenv("GPUQ_NO_FUSED_VALAGG") != nullptr;
+  if (const char* e = getenv("GPUQ_VALAGG_BLOCKS"))
+    plan->valagg_blocks = std::max(1, atoi(e));
+  if (const char* e = getenv("GPUQ_DICT_WALK"))
+    plan->dict_serial = strcmp(e, "serial") == 0;
+  // COUNT(DISTINCT) knobs. The bitmap stays below 2^31 bits so the emit
+  // pass's u32 list cursor cannot wrap; the pair cap can only be lowered.
+  if (const char* e = getenv("GPUQ_DISTINCT_BITMAP_BITS"))
+    plan->distinct_bitmap_bits =
+        std::min<uint64_t>(strtoull(e, nullptr, 10), 1ull << 31);
+  if (const char* e = getenv("GPUQ_DISTINCT_LDS_BITS"))
+    plan->distinct_lds_bits =
+        std::min<uint64_t>(strtoull(e, nullptr, 10), 64 * 1024 * 8);
+  if (const char* e = getenv("GPUQ_DISTINCT_PAIR_CAP"))
+    plan->distinct_pair_cap = (uint32_t)std::min<uint64_t>(
+        std::max<uint64_t>(strtoull(e, nullptr, 10), 1), DISTINCT_PAIR_CAP);
+  if (const char* e = getenv("GPUQ_DISTINCT_FORCE_HASH"))
+    plan->distinct_force_hash = atoi(e) != 0;
+}
 
 int find_or_add_col(std::vector<ColPlan>& cols, const std::string& name) {
   for (size_t i = 0; i < cols.size(); i++)
@@ -756,6 +779,28 @@ uint32_t parse_def1(const uint8_t* data, uint32_t nv, std::vector<uint8_t>& defs
   return 4 + dl;
 }
 
+// One PLAIN byte-array page: the [u32 len][bytes] chain behind the optional
+// def levels. visit(pos, len) per non-null value, pos the page-relative
+// offset of its length field. Positions are 64-bit, so a length that would
+// wrap 32-bit arithmetic is an overrun like any other: returns false.
+template <class Visit>
+bool walk_plain_bytes(const uint8_t* data, uint32_t uncomp_size,
+                      uint32_t num_values, bool optional, Visit&& visit) {
+  std::vector<uint8_t> defs;
+  uint64_t pos = optional ? parse_def1(data, num_values, defs) : 0;
+  for (uint32_t v = 0; v < num_values; v++) {
+    if (optional && !defs[v]) continue;
+    if (pos + 4 > uncomp_size) return false;
+    uint32_t len;
+    memcpy(&len, data + pos, 4);
+    const uint64_t rec = 4ull + len;
+    if (pos + rec > uncomp_size) return false;
+    visit((uint32_t)pos, len);
+    pos += rec;
+  }
+  return true;
+}
+
 int64_t now_ns() {
   struct timespec ts;
   clock_gettime(CLOCK_MONOTONIC, &ts);
@@ -806,6 +851,33 @@ void parallel_for(size_t n, F&& fn, size_t max_threads = 0) {
   for (size_t t = 0; t < nthreads; t++) pool.emplace_back(worker);
   for (auto& th : pool) th.join();
   if (eptr) std::rethrow_exception(eptr);
+}
+
+// One record stream of the phase-5 merge: offsets by prefix sum, resize,
+// then every chunk copies its slice in parallel, rebase(element, chunk)
+// applied on the way where the records carry indices into another merged
+// stream. Returns the per-chunk offsets (what such a rebase adds).
+template <class C, class T, class B, class Rebase>
+std::vector<size_t> merge_stream(std::vector<C>& cbs, std::vector<T> B::*src,
+                                 std::vector<T>& dst, Rebase&& rebase) {
+  const size_t nc = cbs.size();
+  std::vector<size_t> off(nc + 1, 0);
+  for (size_t i = 0; i < nc; i++) off[i + 1] = off[i] + (cbs[i].*src).size();
+  dst.resize(off[nc]);
+  parallel_for(nc, [&](size_t i) {
+    const std::vector<T>& s = cbs[i].*src;
+    for (size_t j = 0; j < s.size(); j++) {
+      T e = s[j];
+      rebase(e, i);
+      dst[off[i] + j] = e;
+    }
+  });
+  return off;
+}
+template <class C, class T, class B>
+std::vector<size_t> merge_stream(std::vector<C>& cbs, std::vector<T> B::*src,
+                                 std::vector<T>& dst) {
+  return merge_stream(cbs, src, dst, [](T&, size_t) {});
 }
 
 Ring::Ring(hipStream_t st) : stream(st) {
@@ -1124,6 +1196,102 @@ void launch_decompress(hipStream_t st, const DecompDev& d) {
   launch_lz4_backrefs(st, d.d_dec, d.d_brs, d.d_pagebrs, d.n_pagebrs);
 }
 
+// GPUQ_PLAN_DEBUG report
+void plan_debug_report(gpuq_plan* plan,
+                       std::map<size_t, std::array<int64_t, 3>>& null_dbg,
+                       const std::vector<std::array<int64_t, 2>>& leaf_dbg,
+                       const std::vector<char>& or_path) {
+  fprintf(stderr, "[gpuq plan] fused_count=%d fused_valagg=%d%s\n",
+          (int)plan->fused_count, (int)plan->fused_valagg,
+          plan->fused_valagg && plan->valagg_late
+              ? " (group count checked at execute)" : "");
+  for (int ai : plan->distinct_aggs) {
+    const auto& c = plan->cols[plan->aggs[ai].col_idx];
+    fprintf(stderr, "[gpuq plan] distinct agg=%d col=%s gids=%s\n", ai,
+            c.name.c_str(),
+            c.numeric_key ? "numeric" : c.hash_mode ? "hash" : "dict");
+  }
+  for (size_t p = 0; p < plan->parts.size(); p++) {
+    const auto& pt = plan->parts[p];
+    // matches an 8 B record could hold: minimal period <= 3
+    size_t period_le3 = 0;
+    for (const DevSeq& r : pt.seqs) {
+      const uint32_t ml = (uint32_t)(r.a >> 49) & 0x1ff;
+      const uint32_t n = std::min(ml, (uint32_t)(r.a >> 58));
+      for (uint32_t q = 1; q <= 3 && ml; q++) {
+        bool ok = true;
+        for (uint32_t j = q; j < n && ok; j++)
+          ok = (uint8_t)(r.pat >> (j * 8)) == (uint8_t)(r.pat >> ((j - q) * 8));
+        if (ok) { period_le3++; break; }
+      }
+    }
+    fprintf(stderr,
+            "[gpuq plan] part %zu: rows=%lld chunks=%zu pages=%zu segs=%zu "
+            "tiles=%zu tile_recs=%zu period_le3=%zu lits_wave=%zu "
+            "res=%zu/%zu pieces=%zu raw=%.2fGB "
+            "dec=%.2fGB cwins=%zu\n",
+            p, (long long)pt.n_rows, pt.chunks.size(), pt.pages.size(),
+            pt.segs.size(), pt.tiles.size(), pt.seqs.size(), period_le3,
+            pt.lits_wave.size(), pt.res_lane.size(), pt.res_wave.size(),
+            pt.piece_pool.size(), pt.raw_bytes / 1e9, pt.dec_bytes / 1e9,
+            pt.cwins.size());
+  }
+  // one line per string / null predicate: the path that evaluates it
+  for (size_t pi = 0; pi < plan->preds.size(); pi++) {
+    const auto& pp = plan->preds[pi];
+    std::string path;
+    if (op_is_like(pp.p.op)) {
+      int ci = find_or_add_col(plan->cols, pp.col);
+      if (plan->cols[ci].hash_mode) {
+        path = "hash";
+      } else {
+        bool lut = false, win = false;
+        int k = plan->ctx_of((int)pi);
+        if (k < 0)  // folded into the LUT of its OR group's context
+          for (auto& f : plan->wfolds)
+            if (f.col == ci) k = f.ctx;
+        for (auto& part : plan->parts) {
+          lut |= part.tasks.count({tk_ctx(TK_DICT_MASK, k), ci}) != 0;
+          win |= part.tasks.count({tk_ctx(TK_BYTES_CONTAINS, k), ci}) != 0;
+        }
+        path = lut && win ? "lut+window" : win ? "window" : lut ? "lut" : "pruned";
+      }
+      fprintf(stderr, "[gpuq plan] pred %zu col=%s op=%s path=%s\n", pi,
+              pp.col.c_str(), op_name(pp.p.op), path.c_str());
+    } else if (op_is_null(pp.p.op)) {
+      const auto& n = null_dbg[pi];
+      static const char* nm[] = {"nulltask", "proven", "pruned"};
+      for (int k = 0; k < 3; k++)
+        if (n[k]) path += (path.empty() ? "" : "+") + std::string(nm[k]);
+      if (path.empty()) path = "pruned";
+      fprintf(stderr,
+              "[gpuq plan] pred %zu col=%s op=%s path=%s rowgroups: "
+              "nulltask=%lld proven=%lld pruned=%lld\n",
+              pi, pp.col.c_str(), op_name(pp.p.op), path.c_str(),
+              (long long)n[0], (long long)n[1], (long long)n[2]);
+    }
+  }
+  if (plan->has_tree) {
+    fprintf(stderr, "[gpuq plan] where %s contexts=%zu depth=%d\n",
+            where_expr(plan->where, plan->where.root).c_str(),
+            plan->ctxs.size(), plan->where.depth);
+    // per leaf: its mask context (-1: folded into a LUT) and how many row
+    // groups evaluate it per row — elision holds inside an OR as well
+    for (size_t pi = 0; pi < plan->preds.size(); pi++)
+      fprintf(stderr,
+              "[gpuq plan] where pred %zu col=%s op=%s ctx=%d rowgroups: "
+              "eval=%lld elided=%lld\n",
+              pi, plan->preds[pi].col.c_str(), op_name(plan->preds[pi].p.op),
+              plan->pred_ctx[pi], (long long)leaf_dbg[pi][0],
+              (long long)leaf_dbg[pi][1]);
+    for (size_t ni = 0; ni < plan->where.nodes.size(); ni++)
+      if (plan->where.nodes[ni].kind == GPUQ_NODE_OR)
+        fprintf(stderr, "[gpuq plan] or node=%zu terms=%zu path=%s\n", ni,
+                plan->where.nodes[ni].kids.size(),
+                or_path[ni] == 'l' ? "lut" : "mask");
+  }
+}
+
 }  // namespace
 
 extern "C" gpuq_plan* gpuq_plan_build(
@@ -1148,6 +1316,7 @@ extern "C" gpuq_plan* gpuq_plan_build_where(
   auto plan = std::make_unique<gpuq_plan>();
   plan->ctx = ctx;
   plan->limit = limit;
+  read_env_knobs(plan.get());
   if (ctx->devices.empty())
     throw std::runtime_error("no GPU devices in session (gpuq never falls back to CPU)");
   if (n_files <= 0)
@@ -1656,10 +1825,9 @@ extern "C" gpuq_plan* gpuq_plan_build_where(
   // decompress, LZ4 structure walks) runs parallel across host cores, with
   // serial phases only for global-dict id assignment and the
   // order-preserving merges into the device pools. ---
-  const bool plan_dbg = getenv("GPUQ_PLAN_DEBUG") != nullptr;
   int64_t tphase = now_ns();
   auto phase_mark = [&](const char* name) {
-    if (!plan_dbg) return;
+    if (!plan->exec_dbg) return;
     int64_t t = now_ns();
     fprintf(stderr, "[gpuq plan] %-22s %7.1f ms\n", name,
             (t - tphase) / 1e6);
@@ -1799,7 +1967,7 @@ extern "C" gpuq_plan* gpuq_plan_build_where(
         // PLAIN pages: walk the [u32 len][bytes] chain once (def-level
         // aware) and record each non-null value's page-relative offset —
         // made absolute in phase 3 once page dst slots are known
-        std::vector<uint8_t> img, defs;
+        std::vector<uint8_t> img;
         bool optional = false;
         {
           int si2 = mf.meta.col_index(c.name);
@@ -1810,25 +1978,13 @@ extern "C" gpuq_plan* gpuq_plan_build_where(
           const uint8_t* data = host_page_payload(
               cm.codec, mf.data + pi.payload_off, pi.comp_size,
               pi.uncomp_size, img);
-          uint32_t pos = 0;
-          const uint32_t nv = pi.num_values;
-          bool has_def = false;
-          if (optional) {
-            pos = parse_def1(data, nv, defs);
-            has_def = true;
-          }
           uint32_t cnt0 = (uint32_t)t.pvals.size();
-          for (uint32_t vI = 0; vI < nv; vI++) {
-            if (has_def && !defs[vI]) continue;
-            if (pos + 4 > (uint32_t)pi.uncomp_size)
-              throw std::runtime_error("plain page overrun (hash col)");
-            uint32_t len;
-            memcpy(&len, data + pos, 4);
-            t.pvals.push_back((int64_t)pos);
-            pos += 4 + len;
-            if (pos > (uint32_t)pi.uncomp_size)
-              throw std::runtime_error("plain page overrun (hash col)");
-          }
+          if (!walk_plain_bytes(data, (uint32_t)pi.uncomp_size,
+                                (uint32_t)pi.num_values, optional,
+                                [&](uint32_t pos, uint32_t) {
+                                  t.pvals.push_back((int64_t)pos);
+                                }))
+            throw std::runtime_error("plain page overrun (hash col)");
           t.pval_page_n.push_back((uint32_t)t.pvals.size() - cnt0);
         }
       }
@@ -2084,69 +2240,23 @@ extern "C" gpuq_plan* gpuq_plan_build_where(
     // copies (with its piece/backref index bases applied) into its slice.
     {
       const size_t nc = cbs.size();
-      std::vector<size_t> o_pages(nc + 1, 0), o_segs(nc + 1, 0),
-          o_brs(nc + 1, 0), o_pagebrs(nc + 1, 0), o_rl(nc + 1, 0),
-          o_rw(nc + 1, 0), o_pp(nc + 1, 0), o_sq(nc + 1, 0),
-          o_ti(nc + 1, 0), o_lw(nc + 1, 0);
-      for (size_t i = 0; i < nc; i++) {
-        const auto& cb = cbs[i];
-        o_pages[i + 1] = o_pages[i] + cb.pages.size();
-        o_segs[i + 1] = o_segs[i] + cb.segs.size();
-        o_brs[i + 1] = o_brs[i] + cb.brs.size();
-        o_pagebrs[i + 1] = o_pagebrs[i] + cb.pagebrs.size();
-        o_rl[i + 1] = o_rl[i] + cb.res_lane.size();
-        o_rw[i + 1] = o_rw[i] + cb.res_wave.size();
-        o_pp[i + 1] = o_pp[i] + cb.piece_pool.size();
-        o_sq[i + 1] = o_sq[i] + cb.seqs.size();
-        o_ti[i + 1] = o_ti[i] + cb.tiles.size();
-        o_lw[i + 1] = o_lw[i] + cb.lits_wave.size();
-      }
-      part.pages.resize(o_pages[nc]);
-      part.segs.resize(o_segs[nc]);
-      part.brs.resize(o_brs[nc]);
-      part.pagebrs.resize(o_pagebrs[nc]);
-      part.res_lane.resize(o_rl[nc]);
-      part.res_wave.resize(o_rw[nc]);
-      part.piece_pool.resize(o_pp[nc]);
-      part.seqs.resize(o_sq[nc]);
-      part.tiles.resize(o_ti[nc]);
-      part.lits_wave.resize(o_lw[nc]);
-      parallel_for(nc, [&](size_t i) {
-        auto& cb = cbs[i];
-        std::copy(cb.pages.begin(), cb.pages.end(),
-                  part.pages.begin() + o_pages[i]);
-        std::copy(cb.segs.begin(), cb.segs.end(),
-                  part.segs.begin() + o_segs[i]);
-        std::copy(cb.brs.begin(), cb.brs.end(), part.brs.begin() + o_brs[i]);
-        const uint32_t br_base = (uint32_t)o_brs[i];
-        for (size_t j = 0; j < cb.pagebrs.size(); j++) {
-          DevPageBr pb = cb.pagebrs[j];
-          pb.start += br_base;
-          part.pagebrs[o_pagebrs[i] + j] = pb;
-        }
-        std::copy(cb.piece_pool.begin(), cb.piece_pool.end(),
-                  part.piece_pool.begin() + o_pp[i]);
-        const uint32_t piece_base = (uint32_t)o_pp[i];
-        for (size_t j = 0; j < cb.res_lane.size(); j++) {
-          DevBrRes r2 = cb.res_lane[j];
-          r2.piece_start += piece_base;
-          part.res_lane[o_rl[i] + j] = r2;
-        }
-        for (size_t j = 0; j < cb.res_wave.size(); j++) {
-          DevBrRes r2 = cb.res_wave[j];
-          r2.piece_start += piece_base;
-          part.res_wave[o_rw[i] + j] = r2;
-        }
-        std::copy(cb.seqs.begin(), cb.seqs.end(),
-                  part.seqs.begin() + o_sq[i]);
-        for (size_t j = 0; j < cb.tiles.size(); j++) {
-          DevSeqTile t2 = cb.tiles[j];
-          t2.rec0 += o_sq[i];
-          part.tiles[o_ti[i] + j] = t2;
-        }
-        std::copy(cb.lits_wave.begin(), cb.lits_wave.end(),
-                  part.lits_wave.begin() + o_lw[i]);
-      });
+      merge_stream(cbs, &CB::pages, part.pages);
+      merge_stream(cbs, &CB::segs, part.segs);
+      const auto o_brs = merge_stream(cbs, &CB::brs, part.brs);
+      merge_stream(cbs, &CB::pagebrs, part.pagebrs,
+                   [&](DevPageBr& pb, size_t i) {
+                     pb.start += (uint32_t)o_brs[i];
+                   });
+      const auto o_pp = merge_stream(cbs, &CB::piece_pool, part.piece_pool);
+      auto piece_rebase = [&](DevBrRes& r, size_t i) {
+        r.piece_start += (uint32_t)o_pp[i];
+      };
+      merge_stream(cbs, &CB::res_lane, part.res_lane, piece_rebase);
+      merge_stream(cbs, &CB::res_wave, part.res_wave, piece_rebase);
+      const auto o_sq = merge_stream(cbs, &CB::seqs, part.seqs);
+      merge_stream(cbs, &CB::tiles, part.tiles,
+                   [&](DevSeqTile& t, size_t i) { t.rec0 += o_sq[i]; });
+      merge_stream(cbs, &CB::lits_wave, part.lits_wave);
       // small, order-sensitive leftovers stay serial
       for (size_t i = 0; i < nc; i++) {
         auto& cb = cbs[i];
@@ -2172,109 +2282,49 @@ extern "C" gpuq_plan* gpuq_plan_build_where(
         std::vector<uint16_t> starts;
       };
       std::vector<CLocal> locals(citems.size());
-      std::atomic<size_t> next{0};
-      std::atomic<bool> failed{false};
-      auto worker = [&]() {
-        std::vector<uint8_t> img, defs;
-        for (;;) {
-          size_t i = next.fetch_add(1);
-          if (i >= citems.size() || failed.load()) return;
-          const auto& it = citems[i];
-          auto& L = locals[i];
-          const uint8_t* data;
-          try {
-            data = host_page_payload(it.codec, it.praw, it.comp, it.uncomp,
-                                     img);
-          } catch (const std::exception&) {
-            failed.store(true);
-            return;
-          }
-          uint32_t pos = 0;
-          const uint32_t nv = it.num_values;
-          bool has_def = false;
-          if (it.optional) {
-            uint32_t dl;
-            std::memcpy(&dl, data, 4);
-            defs.assign(nv, 1);
-            // def bit-width 1 RLE/bit-packed hybrid (parquet-format RLE)
-            const uint8_t* p = data + 4;
-            const uint8_t* end = p + dl;
-            uint32_t v = 0;
-            while (v < nv && p < end) {
-              uint64_t hdr = 0;
-              int sh = 0;
-              for (;;) {
-                uint8_t b = *p++;
-                hdr |= (uint64_t)(b & 0x7f) << sh;
-                if (!(b & 0x80)) break;
-                sh += 7;
-              }
-              if (hdr & 1) {
-                uint32_t groups = (uint32_t)(hdr >> 1);
-                for (uint32_t g = 0; g < groups; g++) {
-                  uint8_t byte = p[g];
-                  for (int j = 0; j < 8; j++) {
-                    uint32_t idx = v + g * 8 + j;
-                    if (idx < nv) defs[idx] = (byte >> j) & 1;
-                  }
-                }
-                p += groups;
-                uint32_t add = groups * 8;
-                v += add > nv - v ? nv - v : add;
-              } else {
-                uint32_t cnt = (uint32_t)(hdr >> 1);
-                uint8_t val = *p++;
-                if (cnt > nv - v) cnt = nv - v;
-                std::fill(defs.begin() + v, defs.begin() + v + cnt, val);
-                v += cnt;
-              }
-            }
-            pos = 4 + dl;
-            has_def = true;
-          }
-          uint32_t dense = 0;
-          int64_t wfirst = -1;
-          uint32_t wbytes = 0, wvals = 0, wdense0 = 0;
-          auto flush = [&]() {
-            if (wfirst < 0) return;
-            L.wins.push_back({it.dst_off + (uint64_t)wfirst,
-                              (uint64_t)(L.starts.size() - wvals), wbytes,
-                              wvals, wdense0, it.page_id});
-            wfirst = -1;
-            wbytes = wvals = 0;
-          };
-          for (uint32_t vI = 0; vI < nv; vI++) {
-            if (has_def && !defs[vI]) continue;
-            if (pos + 4 > (uint32_t)it.uncomp) { failed.store(true); return; }
-            uint32_t len;
-            std::memcpy(&len, data + pos, 4);
-            uint64_t rec = 4ull + len;
-            if (pos + rec > (uint64_t)it.uncomp) { failed.store(true); return; }
-            if (rec > 16384) {  // oversized value: its own window
-              flush();
-              L.starts.push_back(0);
-              L.wins.push_back({it.dst_off + pos, L.starts.size() - 1,
-                                (uint32_t)rec, 1, dense, it.page_id});
-            } else {
-              if (wfirst >= 0 && wbytes + rec > 16384) flush();
-              if (wfirst < 0) { wfirst = pos; wdense0 = dense; }
-              L.starts.push_back((uint16_t)(pos - wfirst));
-              wbytes += (uint32_t)rec;
-              wvals++;
-            }
-            pos += (uint32_t)rec;
-            dense++;
-          }
-          flush();
+      const char* const corrupt = "contains window walk failed (corrupt page)";
+      parallel_for(citems.size(), [&](size_t i) {
+        const auto& it = citems[i];
+        auto& L = locals[i];
+        std::vector<uint8_t> img;
+        const uint8_t* data;
+        try {
+          data = host_page_payload(it.codec, it.praw, it.comp, it.uncomp, img);
+        } catch (const std::exception&) {
+          throw std::runtime_error(corrupt);
         }
-      };
-      size_t nthreads = std::min<size_t>(
-          std::max(1u, std::thread::hardware_concurrency()), citems.size());
-      std::vector<std::thread> pool;
-      for (size_t i = 0; i < nthreads; i++) pool.emplace_back(worker);
-      for (auto& th : pool) th.join();
-      if (failed.load())
-        throw std::runtime_error("contains window walk failed (corrupt page)");
+        uint32_t dense = 0;
+        int64_t wfirst = -1;
+        uint32_t wbytes = 0, wvals = 0, wdense0 = 0;
+        auto flush = [&]() {
+          if (wfirst < 0) return;
+          L.wins.push_back({it.dst_off + (uint64_t)wfirst,
+                            (uint64_t)(L.starts.size() - wvals), wbytes,
+                            wvals, wdense0, it.page_id});
+          wfirst = -1;
+          wbytes = wvals = 0;
+        };
+        if (!walk_plain_bytes(
+                data, (uint32_t)it.uncomp, it.num_values, it.optional,
+                [&](uint32_t pos, uint32_t len) {
+                  const uint64_t rec = 4ull + len;
+                  if (rec > 16384) {  // oversized value: its own window
+                    flush();
+                    L.starts.push_back(0);
+                    L.wins.push_back({it.dst_off + pos, L.starts.size() - 1,
+                                      (uint32_t)rec, 1, dense, it.page_id});
+                  } else {
+                    if (wfirst >= 0 && wbytes + rec > 16384) flush();
+                    if (wfirst < 0) { wfirst = pos; wdense0 = dense; }
+                    L.starts.push_back((uint16_t)(pos - wfirst));
+                    wbytes += (uint32_t)rec;
+                    wvals++;
+                  }
+                  dense++;
+                }))
+          throw std::runtime_error(corrupt);
+        flush();
+      });
       // append in task order, per column
       std::map<int32_t, size_t> by_page;
       for (size_t i = 0; i < citems.size(); i++) by_page[citems[i].page_id] = i;
@@ -2401,31 +2451,13 @@ extern "C" gpuq_plan* gpuq_plan_build_where(
       if (t.cm->null_count != 0) part.col_null_free[t.col_idx] = 0;
   }
 
-  // fused value-decode + aggregate: exactly the shape launch_agg's fast path
-  // takes with two aggregates, over a column that only the aggregate reads
-  // and whose pages are all dict-encoded or PLAIN 8-byte
-  plan->exec_dbg = getenv("GPUQ_PLAN_DEBUG") != nullptr;
-  if (const char* e = getenv("GPUQ_VALAGG_BLOCKS"))
-    plan->valagg_blocks = std::max(1, atoi(e));
-  if (const char* e = getenv("GPUQ_DICT_WALK"))
-    plan->dict_serial = strcmp(e, "serial") == 0;
-  // COUNT(DISTINCT) knobs. The bitmap stays below 2^31 bits so the emit
-  // pass's u32 list cursor cannot wrap; the pair cap can only be lowered.
-  if (const char* e = getenv("GPUQ_DISTINCT_BITMAP_BITS"))
-    plan->distinct_bitmap_bits =
-        std::min<uint64_t>(strtoull(e, nullptr, 10), 1ull << 31);
-  if (const char* e = getenv("GPUQ_DISTINCT_LDS_BITS"))
-    plan->distinct_lds_bits =
-        std::min<uint64_t>(strtoull(e, nullptr, 10), 64 * 1024 * 8);
-  if (const char* e = getenv("GPUQ_DISTINCT_PAIR_CAP"))
-    plan->distinct_pair_cap = (uint32_t)std::min<uint64_t>(
-        std::max<uint64_t>(strtoull(e, nullptr, 10), 1), DISTINCT_PAIR_CAP);
-  if (const char* e = getenv("GPUQ_DISTINCT_FORCE_HASH"))
-    plan->distinct_force_hash = atoi(e) != 0;
   // a distinct agg keeps the plan off both fused paths (their shapes admit
   // no third kind of aggregate; stated here so a later shape cannot let one in)
   if (!plan->distinct_aggs.empty()) plan->fused_count = false;
-  if (!plan->is_projection && !getenv("GPUQ_NO_FUSED_VALAGG") &&
+  // fused value-decode + aggregate: exactly the shape launch_agg's fast path
+  // takes with two aggregates, over a column that only the aggregate reads
+  // and whose pages are all dict-encoded or PLAIN 8-byte
+  if (!plan->is_projection && !plan->no_fused_valagg &&
       plan->distinct_aggs.empty() &&
       plan->group_cols.size() == 1 && plan->aggs.size() == 2 &&
       plan->aggs[0].kind == AGGK_COUNT_STAR && plan->n_fsum == 0 &&
@@ -2467,97 +2499,8 @@ extern "C" gpuq_plan* gpuq_plan_build_where(
     }
   }
 
-  if (getenv("GPUQ_PLAN_DEBUG")) {
-    fprintf(stderr, "[gpuq plan] fused_count=%d fused_valagg=%d%s\n",
-            (int)plan->fused_count, (int)plan->fused_valagg,
-            plan->fused_valagg && plan->valagg_late
-                ? " (group count checked at execute)" : "");
-    for (int ai : plan->distinct_aggs) {
-      const auto& c = plan->cols[plan->aggs[ai].col_idx];
-      fprintf(stderr, "[gpuq plan] distinct agg=%d col=%s gids=%s\n", ai,
-              c.name.c_str(),
-              c.numeric_key ? "numeric" : c.hash_mode ? "hash" : "dict");
-    }
-    for (size_t p = 0; p < plan->parts.size(); p++) {
-      const auto& pt = plan->parts[p];
-      // matches an 8 B record could hold: minimal period <= 3
-      size_t period_le3 = 0;
-      for (const DevSeq& r : pt.seqs) {
-        const uint32_t ml = (uint32_t)(r.a >> 49) & 0x1ff;
-        const uint32_t n = std::min(ml, (uint32_t)(r.a >> 58));
-        for (uint32_t q = 1; q <= 3 && ml; q++) {
-          bool ok = true;
-          for (uint32_t j = q; j < n && ok; j++)
-            ok = (uint8_t)(r.pat >> (j * 8)) == (uint8_t)(r.pat >> ((j - q) * 8));
-          if (ok) { period_le3++; break; }
-        }
-      }
-      fprintf(stderr,
-              "[gpuq plan] part %zu: rows=%lld chunks=%zu pages=%zu segs=%zu "
-              "tiles=%zu tile_recs=%zu period_le3=%zu lits_wave=%zu "
-              "res=%zu/%zu pieces=%zu raw=%.2fGB "
-              "dec=%.2fGB cwins=%zu\n",
-              p, (long long)pt.n_rows, pt.chunks.size(), pt.pages.size(),
-              pt.segs.size(), pt.tiles.size(), pt.seqs.size(), period_le3,
-              pt.lits_wave.size(), pt.res_lane.size(), pt.res_wave.size(),
-              pt.piece_pool.size(), pt.raw_bytes / 1e9, pt.dec_bytes / 1e9,
-              pt.cwins.size());
-    }
-    // one line per string / null predicate: the path that evaluates it
-    for (size_t pi = 0; pi < plan->preds.size(); pi++) {
-      const auto& pp = plan->preds[pi];
-      std::string path;
-      if (op_is_like(pp.p.op)) {
-        int ci = find_or_add_col(plan->cols, pp.col);
-        if (plan->cols[ci].hash_mode) {
-          path = "hash";
-        } else {
-          bool lut = false, win = false;
-          int k = plan->ctx_of((int)pi);
-          if (k < 0)  // folded into the LUT of its OR group's context
-            for (auto& f : plan->wfolds)
-              if (f.col == ci) k = f.ctx;
-          for (auto& part : plan->parts) {
-            lut |= part.tasks.count({tk_ctx(TK_DICT_MASK, k), ci}) != 0;
-            win |= part.tasks.count({tk_ctx(TK_BYTES_CONTAINS, k), ci}) != 0;
-          }
-          path = lut && win ? "lut+window" : win ? "window" : lut ? "lut" : "pruned";
-        }
-        fprintf(stderr, "[gpuq plan] pred %zu col=%s op=%s path=%s\n", pi,
-                pp.col.c_str(), op_name(pp.p.op), path.c_str());
-      } else if (op_is_null(pp.p.op)) {
-        const auto& n = null_dbg[pi];
-        static const char* nm[] = {"nulltask", "proven", "pruned"};
-        for (int k = 0; k < 3; k++)
-          if (n[k]) path += (path.empty() ? "" : "+") + std::string(nm[k]);
-        if (path.empty()) path = "pruned";
-        fprintf(stderr,
-                "[gpuq plan] pred %zu col=%s op=%s path=%s rowgroups: "
-                "nulltask=%lld proven=%lld pruned=%lld\n",
-                pi, pp.col.c_str(), op_name(pp.p.op), path.c_str(),
-                (long long)n[0], (long long)n[1], (long long)n[2]);
-      }
-    }
-    if (plan->has_tree) {
-      fprintf(stderr, "[gpuq plan] where %s contexts=%zu depth=%d\n",
-              where_expr(plan->where, plan->where.root).c_str(),
-              plan->ctxs.size(), plan->where.depth);
-      // per leaf: its mask context (-1: folded into a LUT) and how many row
-      // groups evaluate it per row — elision holds inside an OR as well
-      for (size_t pi = 0; pi < plan->preds.size(); pi++)
-        fprintf(stderr,
-                "[gpuq plan] where pred %zu col=%s op=%s ctx=%d rowgroups: "
-                "eval=%lld elided=%lld\n",
-                pi, plan->preds[pi].col.c_str(), op_name(plan->preds[pi].p.op),
-                plan->pred_ctx[pi], (long long)leaf_dbg[pi][0],
-                (long long)leaf_dbg[pi][1]);
-      for (size_t ni = 0; ni < plan->where.nodes.size(); ni++)
-        if (plan->where.nodes[ni].kind == GPUQ_NODE_OR)
-          fprintf(stderr, "[gpuq plan] or node=%zu terms=%zu path=%s\n", ni,
-                  plan->where.nodes[ni].kids.size(),
-                  or_path[ni] == 'l' ? "lut" : "mask");
-    }
-  }
+  if (plan->exec_dbg)
+    plan_debug_report(plan.get(), null_dbg, leaf_dbg, or_path);
   return plan.release();
 } catch (const std::exception& e) {
   if (ctx) ctx->set_error(e.what());
@@ -2947,13 +2890,14 @@ const char* ss_get_last_error(struct ArrowArrayStream* st) {
   auto* s = (StreamState*)st->private_data;
   return s->err.empty() ? nullptr : s->err.c_str();
 }
+void stream_state_free(StreamState* s) {
+  if (s->schema.release) release_schema(&s->schema);
+  if (s->batch.release) release_array(&s->batch);
+  delete s;
+}
 void ss_release(struct ArrowArrayStream* st) {
   auto* s = (StreamState*)st->private_data;
-  if (s) {
-    if (s->schema.release) release_schema(&s->schema);
-    if (s->batch.release) release_array(&s->batch);
-    delete s;
-  }
+  if (s) stream_state_free(s);
   st->release = nullptr;
 }
 
@@ -3087,15 +3031,16 @@ const char* proj_get_last_error(struct ArrowArrayStream* st0) {
   auto* s = (ProjState*)st0->private_data;
   return s->err.empty() ? nullptr : s->err.c_str();
 }
+void proj_state_free(ProjState* s) {
+  if (s->schema.release) release_schema(&s->schema);
+  if (s->d_g64) (void)hipFree(s->d_g64);
+  if (s->d_g32) (void)hipFree(s->d_g32);
+  if (s->d_g8) (void)hipFree(s->d_g8);
+  delete s;
+}
 void proj_release(struct ArrowArrayStream* st0) {
   auto* s = (ProjState*)st0->private_data;
-  if (s) {
-    if (s->schema.release) release_schema(&s->schema);
-    if (s->d_g64) (void)hipFree(s->d_g64);
-    if (s->d_g32) (void)hipFree(s->d_g32);
-    if (s->d_g8) (void)hipFree(s->d_g8);
-    delete s;
-  }
+  if (s) proj_state_free(s);
   st0->release = nullptr;
 }
 
@@ -3239,10 +3184,159 @@ int proj_get_next(struct ArrowArrayStream* st0, struct ArrowArray* out) try {
 
 }  // namespace
 
-int32_t execute_projection(gpuq_plan* plan, Partition& part, hipStream_t st,
-                           hipEvent_t ev0, hipEvent_t ev1, hipEvent_t ev_decomp,
-                           int64_t t0, bool need_mask,
-                           struct ArrowArrayStream* out) {
+// The three events of one execute: created at entry, destroyed on every exit.
+struct ExecEvents {
+  hipEvent_t ev0 = nullptr, ev1 = nullptr, decomp = nullptr;
+  ExecEvents() = default;
+  ExecEvents(const ExecEvents&) = delete;
+  ExecEvents& operator=(const ExecEvents&) = delete;
+  void create() {
+    HIP_TRY(hipEventCreate(&ev0));
+    HIP_TRY(hipEventCreate(&ev1));
+    HIP_TRY(hipEventCreate(&decomp));
+  }
+  ~ExecEvents() {
+    for (hipEvent_t e : {ev0, ev1, decomp})
+      if (e) (void)hipEventDestroy(e);
+  }
+};
+
+// GPUQ_EQ..GE -> CMP_*; -1 for every other op (the callers own BETWEEN and
+// the LIKE family)
+int cmp_mode_of(int op) {
+  switch (op) {
+    case GPUQ_EQ: return CMP_EQ;
+    case GPUQ_NE: return CMP_NE;
+    case GPUQ_LT: return CMP_LT;
+    case GPUQ_LE: return CMP_LE;
+    case GPUQ_GT: return CMP_GT;
+    case GPUQ_GE: return CMP_GE;
+    default: return -1;
+  }
+}
+
+// ---- Arrow column builders over ExportedBatch::grab ----------------------
+// Each fills n_buffers / buffers / null_count of a child whose length is
+// set; buffers[0] stays nullptr when the column has no nulls.
+
+// int64 (or f64 bit pattern) values; valid: one byte per row, 0 = NULL
+// (nullptr: no nulls)
+void set_i64_column(ExportedBatch& eb, struct ArrowArray* ch,
+                    const std::vector<int64_t>& vals,
+                    const std::vector<uint8_t>* valid = nullptr) {
+  const size_t n = vals.size();
+  ch->n_buffers = 2;
+  ch->buffers = (const void**)calloc(2, sizeof(void*));
+  int64_t* v = (int64_t*)eb.grab(n * 8);
+  if (n) memcpy(v, vals.data(), n * 8);
+  ch->buffers[1] = v;
+  if (!valid) return;
+  uint8_t* validity = (uint8_t*)eb.grab((n + 7) / 8);
+  memset(validity, 0xff, (n + 7) / 8);
+  int64_t nulls = 0;
+  for (size_t r = 0; r < n; r++)
+    if (!(*valid)[r]) {
+      validity[r / 8] &= (uint8_t)~(1 << (r % 8));
+      nulls++;
+    }
+  if (nulls) { ch->buffers[0] = validity; ch->null_count = nulls; }
+}
+
+// utf8 from one string pointer per row, NULL where it is nullptr
+void set_utf8_column(ExportedBatch& eb, struct ArrowArray* ch,
+                     const std::vector<const std::string*>& strs) {
+  const size_t n = strs.size();
+  ch->n_buffers = 3;
+  ch->buffers = (const void**)calloc(3, sizeof(void*));
+  uint8_t* validity = (uint8_t*)eb.grab((n + 7) / 8);
+  memset(validity, 0xff, (n + 7) / 8);
+  int32_t* offs = (int32_t*)eb.grab((n + 1) * 4);
+  size_t total = 0;
+  for (const std::string* s : strs)
+    if (s) total += s->size();
+  char* data = (char*)eb.grab(total);
+  size_t off = 0;
+  int64_t nulls = 0;
+  for (size_t r = 0; r < n; r++) {
+    offs[r] = (int32_t)off;
+    if (strs[r]) {
+      memcpy(data + off, strs[r]->data(), strs[r]->size());
+      off += strs[r]->size();
+    } else {
+      validity[r / 8] &= (uint8_t)~(1 << (r % 8));
+      nulls++;
+    }
+  }
+  offs[n] = (int32_t)off;
+  if (nulls) { ch->buffers[0] = validity; ch->null_count = nulls; }
+  ch->buffers[1] = offs;
+  ch->buffers[2] = data;
+}
+
+// list offsets (rows + 1 entries); the caller attaches the item child
+void set_list_offsets(ExportedBatch& eb, struct ArrowArray* ch,
+                      const std::vector<int32_t>& offs) {
+  ch->n_buffers = 2;
+  ch->buffers = (const void**)calloc(2, sizeof(void*));
+  int32_t* o = (int32_t*)eb.grab(offs.size() * 4);
+  memcpy(o, offs.data(), offs.size() * 4);
+  ch->buffers[1] = o;
+}
+
+// the count slot of aggregate i in one group's table row (base = its first
+// slot). count(*) == presence: k_agg spends no atomics on its slots; same
+// for any agg whose column is footer-proven null-free (cnt_is_presence)
+uint64_t agg_count(const std::vector<uint64_t>& table, size_t base, int i,
+                   int kind, bool cnt_is_presence) {
+  return (kind == AGGK_COUNT_STAR || cnt_is_presence) ? table[base]
+                                                      : table[base + 2 + 2 * i];
+}
+
+// reset the shared open-addressing table (keys, gids, claim counter) over
+// `slots` entries: each site keeps its own size
+void reset_hash_table(Partition& part, hipStream_t st, uint64_t slots) {
+  HIP_TRY(hipMemsetAsync(part.d_hkeys, 0xFF, slots * 8, st));
+  HIP_TRY(hipMemsetAsync(part.d_hgids, 0xFF, slots * 4, st));
+  HIP_TRY(hipMemsetAsync(part.d_hcount, 0, 4, st));
+}
+// the claimed count of the build just enqueued (synchronises the stream)
+uint32_t read_claimed(Partition& part, hipStream_t st) {
+  uint32_t claimed = 0;
+  HIP_TRY(hipMemcpyAsync(&claimed, part.d_hcount, 4, hipMemcpyDeviceToHost,
+                         st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return claimed;
+}
+
+// One of the four value-decode kinds (TK_DICT_GID, TK_DICT_VAL, TK_PLAIN_VAL,
+// TK_POOL_VAL) through its launcher launch(dst, valid, present, mode).
+// Footer-proven null-free column: the direct decode alone, validity asserted
+// (mode 2) — the def-level pass, the scratch decode and the expansion would
+// each find nothing to do. Otherwise def levels, the direct decode of
+// null-free pages (mode 0), the dense decode of the others into d_scr
+// (mode 1) and its expansion to row positions.
+template <class Launch>
+void decode_values(Partition& part, hipStream_t st, const int32_t* ids, int n,
+                   bool null_free, Launch&& launch, void* dst, uint8_t* valid,
+                   uint8_t* levels_valid, int expand_mode) {
+  if (null_free) {
+    launch(dst, valid, nullptr, 2);
+    return;
+  }
+  launch_def_levels(st, part.d_dec, part.d_pages, ids, n, levels_valid,
+                    nullptr, nullptr, part.d_rank, part.d_present, part.d_err);
+  launch(dst, valid, part.d_present, 0);
+  launch(part.d_scr, nullptr, part.d_present, 1);
+  launch_expand(st, part.d_dec, part.d_pages, ids, n, part.d_scr, part.d_rank,
+                levels_valid, (uint8_t*)dst, expand_mode);
+}
+
+int32_t execute_projection(gpuq_plan* plan, Partition& part,
+                           const ExecEvents& events, int64_t t0,
+                           bool need_mask, struct ArrowArrayStream* out) {
+  hipStream_t st = part.stream;
+  const hipEvent_t ev0 = events.ev0, ev1 = events.ev1,
+                   ev_decomp = events.decomp;
   // compact selected (ts,row) pairs -> radix sort desc -> batched gather
   HIP_TRY(hipMemsetAsync(part.d_count, 0, 8, st));
   launch_compact(st, need_mask ? part.d_mask : nullptr,
@@ -3268,19 +3362,19 @@ int32_t execute_projection(gpuq_plan* plan, Partition& part, hipStream_t st,
   float ms_total = 0, ms_decomp = 0;
   HIP_TRY(hipEventElapsedTime(&ms_total, ev0, ev1));
   HIP_TRY(hipEventElapsedTime(&ms_decomp, ev0, ev_decomp));
-  HIP_TRY(hipEventDestroy(ev0));
-  HIP_TRY(hipEventDestroy(ev1));
-  HIP_TRY(hipEventDestroy(ev_decomp));
 
   int np = (int)plan->projection.size();
-  auto* ps = new ProjState();
+  // owned here until `out` takes it: a throw below frees the schema and the
+  // three device buffers through the stream's own release path
+  std::unique_ptr<ProjState, void (*)(ProjState*)> ps(new ProjState(),
+                                                      proj_state_free);
+  memset(&ps->schema, 0, sizeof(ps->schema));
   ps->plan = plan;
   ps->part = &part;
   ps->total = k;
   HIP_TRY(hipMalloc(&ps->d_g64, PROJ_BATCH * 8));
   HIP_TRY(hipMalloc(&ps->d_g32, PROJ_BATCH * 4));
   HIP_TRY(hipMalloc(&ps->d_g8, PROJ_BATCH));
-  memset(&ps->schema, 0, sizeof(ps->schema));
   ps->schema.format = strdup("+s");
   ps->schema.name = strdup("");
   ps->schema.release = release_schema;
@@ -3298,7 +3392,7 @@ int32_t execute_projection(gpuq_plan* plan, Partition& part, hipStream_t st,
   out->get_next = proj_get_next;
   out->get_last_error = proj_get_last_error;
   out->release = proj_release;
-  out->private_data = ps;
+  out->private_data = ps.release();
 
   {
     std::lock_guard<std::mutex> g(plan->mu);
@@ -3324,10 +3418,10 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
   int64_t t0 = now_ns();
   const bool dw = plan->dict_serial;  // serial_walk of the dict launches
 
-  hipEvent_t ev0, ev1, ev_decomp;
-  HIP_TRY(hipEventCreate(&ev0));
-  HIP_TRY(hipEventCreate(&ev1));
-  HIP_TRY(hipEventCreate(&ev_decomp));
+  ExecEvents events;  // destroyed on every exit, a throw included
+  events.create();
+  const hipEvent_t ev0 = events.ev0, ev1 = events.ev1,
+                   ev_decomp = events.decomp;
 
   // a query whose every predicate is chunk-stats-proven everywhere needs no
   // selection mask at all (string/contains preds are never elided, so their
@@ -3399,102 +3493,63 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
       d_lut += (size_t)(std::find(lc.begin(), lc.end(), kctx) - lc.begin()) *
                part.lut_pool.size();
     }
-    // footer-proven null-free column: the direct decode alone, validity
-    // asserted (mode 2) — the def-level pass, the scratch decode and the
-    // expansion would each find nothing to do
-    if (part.col_null_free[col]) {
-      switch (kind) {
-        case TK_DICT_GID: {
-          auto it = part.d_valid.find(col);
-          launch_dict_gid(st, part.d_dec, part.d_pages, ids, n, part.d_remap,
-                          part.d_gid[col],
-                          it != part.d_valid.end() ? it->second : nullptr,
-                          nullptr, 2, dw, part.d_err);
-          return;
-        }
-        case TK_DICT_VAL:
-          launch_dict_i64(st, part.d_dec, part.d_pages, ids, n, part.d_dictv,
-                          part.d_val[col], part.d_valid[col], nullptr, 2,
-                          dw, part.d_err);
-          return;
-        case TK_PLAIN_VAL:
-          launch_plain_fixed(st, part.d_dec, part.d_pages, ids, n,
-                             part.d_val[col], part.d_valid[col], nullptr, 2,
-                             part.d_err);
-          return;
-        case TK_POOL_VAL:
-          launch_pool_vals(st, part.d_dec, part.d_pages, ids, n, part.d_dictv,
-                           part.d_val[col], part.d_valid[col], nullptr, 2);
-          return;
-        case TK_DICT_MASK:
-          launch_dict_mask(st, part.d_dec, part.d_pages, ids, n, d_lut,
-                           mk, 2, dw, part.d_err);
-          return;
-        default: break;  // delta has one launch already; contains needs rowof
-      }
-    }
+    // footer-proven null-free column: the direct decode alone (mode 2)
+    const bool null_free = part.col_null_free[col] != 0;
     switch (kind) {
       case TK_DICT_GID: {
+        // a column without a validity array of its own (gid only) still
+        // needs one for the def levels and the expansion: d_tmpvalid
         auto it = part.d_valid.find(col);
-        uint8_t* v = it != part.d_valid.end() ? it->second : part.d_tmpvalid;
-        launch_def_levels(st, part.d_dec, part.d_pages, ids, n, v, nullptr,
-                          nullptr, part.d_rank, part.d_present, part.d_err);
-        launch_dict_gid(st, part.d_dec, part.d_pages, ids, n, part.d_remap,
-                        part.d_gid[col],
-                        it != part.d_valid.end() ? it->second : nullptr,
-                        part.d_present, 0, dw, part.d_err);
-        launch_dict_gid(st, part.d_dec, part.d_pages, ids, n, part.d_remap,
-                        (int32_t*)part.d_scr, nullptr, part.d_present, 1,
-                        dw, part.d_err);
-        launch_expand(st, part.d_dec, part.d_pages, ids, n, part.d_scr,
-                      part.d_rank, v, (uint8_t*)part.d_gid[col], 1);
+        uint8_t* valid = it != part.d_valid.end() ? it->second : nullptr;
+        decode_values(
+            part, st, ids, n, null_free,
+            [&](void* dst, uint8_t* v, const uint32_t* present, int mode) {
+              launch_dict_gid(st, part.d_dec, part.d_pages, ids, n,
+                              part.d_remap, (int32_t*)dst, v, present, mode,
+                              dw, part.d_err);
+            },
+            part.d_gid[col], valid, valid ? valid : part.d_tmpvalid, 1);
         break;
       }
       case TK_DICT_VAL:
-        launch_def_levels(st, part.d_dec, part.d_pages, ids, n,
-                          part.d_valid[col], nullptr, nullptr,
-                          part.d_rank, part.d_present, part.d_err);
-        launch_dict_i64(st, part.d_dec, part.d_pages, ids, n, part.d_dictv,
-                        part.d_val[col], part.d_valid[col], part.d_present, 0,
-                        dw, part.d_err);
-        launch_dict_i64(st, part.d_dec, part.d_pages, ids, n, part.d_dictv,
-                        (int64_t*)part.d_scr, nullptr, part.d_present, 1,
-                        dw, part.d_err);
-        launch_expand(st, part.d_dec, part.d_pages, ids, n, part.d_scr,
-                      part.d_rank, part.d_valid[col],
-                      (uint8_t*)part.d_val[col], 0);
+        decode_values(
+            part, st, ids, n, null_free,
+            [&](void* dst, uint8_t* v, const uint32_t* present, int mode) {
+              launch_dict_i64(st, part.d_dec, part.d_pages, ids, n,
+                              part.d_dictv, (int64_t*)dst, v, present, mode,
+                              dw, part.d_err);
+            },
+            part.d_val[col], part.d_valid[col], part.d_valid[col], 0);
         break;
       case TK_PLAIN_VAL:
-        launch_def_levels(st, part.d_dec, part.d_pages, ids, n,
-                          part.d_valid[col], nullptr, nullptr,
-                          part.d_rank, part.d_present, part.d_err);
-        launch_plain_fixed(st, part.d_dec, part.d_pages, ids, n,
-                           part.d_val[col], part.d_valid[col], part.d_present,
-                           0, part.d_err);
-        launch_plain_fixed(st, part.d_dec, part.d_pages, ids, n,
-                           (int64_t*)part.d_scr, nullptr, part.d_present, 1,
-                           part.d_err);
-        launch_expand(st, part.d_dec, part.d_pages, ids, n, part.d_scr,
-                      part.d_rank, part.d_valid[col],
-                      (uint8_t*)part.d_val[col], 0);
+        decode_values(
+            part, st, ids, n, null_free,
+            [&](void* dst, uint8_t* v, const uint32_t* present, int mode) {
+              launch_plain_fixed(st, part.d_dec, part.d_pages, ids, n,
+                                 (int64_t*)dst, v, present, mode, part.d_err);
+            },
+            part.d_val[col], part.d_valid[col], part.d_valid[col], 0);
         break;
       case TK_POOL_VAL:  // PLAIN byte-array pages of hash cols -> strrefs
-        launch_def_levels(st, part.d_dec, part.d_pages, ids, n,
-                          part.d_valid[col], nullptr, nullptr,
-                          part.d_rank, part.d_present, part.d_err);
-        launch_pool_vals(st, part.d_dec, part.d_pages, ids, n, part.d_dictv,
-                         part.d_val[col], part.d_valid[col], part.d_present, 0);
-        launch_pool_vals(st, part.d_dec, part.d_pages, ids, n, part.d_dictv,
-                         (int64_t*)part.d_scr, nullptr, part.d_present, 1);
-        launch_expand(st, part.d_dec, part.d_pages, ids, n, part.d_scr,
-                      part.d_rank, part.d_valid[col],
-                      (uint8_t*)part.d_val[col], 0);
+        decode_values(
+            part, st, ids, n, null_free,
+            [&](void* dst, uint8_t* v, const uint32_t* present, int mode) {
+              launch_pool_vals(st, part.d_dec, part.d_pages, ids, n,
+                               part.d_dictv, (int64_t*)dst, v, present, mode);
+            },
+            part.d_val[col], part.d_valid[col], part.d_valid[col], 0);
         break;
       case TK_DELTA_VAL:
         launch_delta_i64(st, part.d_dec, part.d_pages, ids, n,
                          part.d_val[col], part.d_valid[col], part.d_err);
         break;
       case TK_DICT_MASK:
+        if (null_free) {
+          launch_dict_mask(st, part.d_dec, part.d_pages, ids, n, d_lut, mk, 2,
+                           dw, part.d_err);
+          break;
+        }
+        // the scratch pass is the LUT byte per dense value, not a decode
         launch_def_levels(st, part.d_dec, part.d_pages, ids, n,
                           part.d_tmpvalid, nullptr, nullptr,
                           part.d_rank, part.d_present, part.d_err);
@@ -3560,11 +3615,8 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
     for (int ci : gid_cols) {
       auto& c = plan->cols[ci];
       if (!c.hash_mode && !c.numeric_key) continue;
-      HIP_TRY(hipMemsetAsync(part.d_hkeys, 0xFF,
-                             ((1ull << HASH_LOG2) + 1) * 8, st));
-      HIP_TRY(hipMemsetAsync(part.d_hgids, 0xFF,
-                             ((1ull << HASH_LOG2) + 1) * 4, st));
-      HIP_TRY(hipMemsetAsync(part.d_hcount, 0, 4, st));
+      // +1 entry: the numeric-key overflow slot (gpuq_plan_load)
+      reset_hash_table(part, st, (1ull << HASH_LOG2) + 1);
       auto itv = part.d_valid.find(ci);
       uint8_t* v = itv != part.d_valid.end() ? itv->second : nullptr;
       if (c.numeric_key) {
@@ -3584,11 +3636,7 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
                            part.d_hkeys, part.d_hgids, HASH_LOG2,
                            part.d_gid[ci]);
       }
-      uint32_t claimed = 0;
-      HIP_TRY(hipMemcpyAsync(&claimed, part.d_hcount, 4,
-                             hipMemcpyDeviceToHost, st));
-      HIP_TRY(hipStreamSynchronize(st));
-      part.hash_claimed[ci] = claimed;
+      part.hash_claimed[ci] = read_claimed(part, st);
     }
   }
   // string predicates of hash-mode columns and numeric comparisons of WHERE
@@ -3600,16 +3648,8 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
       for (int pidx : c.lut_preds) {
         if (plan->ctx_of(pidx) != k) continue;
         const auto& pp = plan->preds[pidx];
-        int op;
-        switch (pp.p.op) {
-          case GPUQ_EQ: op = CMP_EQ; break;
-          case GPUQ_NE: op = CMP_NE; break;
-          case GPUQ_LT: op = CMP_LT; break;
-          case GPUQ_LE: op = CMP_LE; break;
-          case GPUQ_GT: op = CMP_GT; break;
-          case GPUQ_GE: op = CMP_GE; break;
-          default: op = cmp_str_like(like_mode(pp.p.op)); break;  // LIKE family
-        }
+        int op = cmp_mode_of(pp.p.op);
+        if (op < 0) op = cmp_str_like(like_mode(pp.p.op));  // LIKE family
         auto itv = part.d_valid.find((int)ci);
         launch_cmp_str(st, part.d_dec, part.d_val[(int)ci],
                        itv != part.d_valid.end() ? itv->second : nullptr,
@@ -3625,17 +3665,8 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
       for (int pidx : c.cmp_preds) {
         if (plan->ctx_of(pidx) != k) continue;
         const auto& pp = plan->preds[pidx];
-        int mode;
-        switch (pp.p.op) {
-          case GPUQ_EQ: mode = CMP_EQ; break;
-          case GPUQ_NE: mode = CMP_NE; break;
-          case GPUQ_LT: mode = CMP_LT; break;
-          case GPUQ_LE: mode = CMP_LE; break;
-          case GPUQ_GT: mode = CMP_GT; break;
-          case GPUQ_GE: mode = CMP_GE; break;
-          case GPUQ_BETWEEN: mode = CMP_RANGE; break;
-          default: throw std::runtime_error("bad cmp op");
-        }
+        int mode = pp.p.op == GPUQ_BETWEEN ? CMP_RANGE : cmp_mode_of(pp.p.op);
+        if (mode < 0) throw std::runtime_error("bad cmp op");
         int is_f64 = (c.phys == PT_DOUBLE) ? 1 : 0;
         int64_t lo = pp.p.i64[0], hi = pp.p.i64[1];
         if (is_f64) {
@@ -3719,20 +3750,14 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
         throw std::runtime_error("group-key cardinality exceeds the 2^22 cap");
       const int32_t* cur = part.d_gid[plan->group_cols[0]];
       for (size_t k = 1; k < plan->group_cols.size(); k++) {
-        HIP_TRY(hipMemsetAsync(part.d_hkeys, 0xFF, (1ull << HASH_LOG2) * 8, st));
-        HIP_TRY(hipMemsetAsync(part.d_hgids, 0xFF, (1ull << HASH_LOG2) * 4, st));
-        HIP_TRY(hipMemsetAsync(part.d_hcount, 0, 4, st));
+        reset_hash_table(part, st, 1ull << HASH_LOG2);
         const int32_t* nxt = part.d_gid[plan->group_cols[k]];
         launch_pair_build(st, cur, nxt, part.n_rows, part.d_hkeys,
                           part.d_hgids, HASH_LOG2, part.d_hcount,
                           part.d_gid2pair[k - 1], GID_CAP, part.d_err);
         launch_pair_lookup(st, cur, nxt, part.n_rows, part.d_hkeys,
                            part.d_hgids, HASH_LOG2, part.d_cgid);
-        uint32_t claimed = 0;
-        HIP_TRY(hipMemcpyAsync(&claimed, part.d_hcount, 4,
-                               hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        level_claimed.push_back(claimed);
+        level_claimed.push_back(read_claimed(part, st));
         cur = part.d_cgid;
       }
       cascaded = true;
@@ -3743,8 +3768,7 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
   }
 
   if (plan->is_projection)
-    return execute_projection(plan, part, st, ev0, ev1, ev_decomp, t0,
-                              need_mask, out);
+    return execute_projection(plan, part, events, t0, need_mask, out);
 
   // 3. aggregate
   AggArgs a{};
@@ -3905,9 +3929,6 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
   float ms_total = 0, ms_decomp = 0;
   HIP_TRY(hipEventElapsedTime(&ms_total, ev0, ev1));
   HIP_TRY(hipEventElapsedTime(&ms_decomp, ev0, ev_decomp));
-  HIP_TRY(hipEventDestroy(ev0));
-  HIP_TRY(hipEventDestroy(ev1));
-  HIP_TRY(hipEventDestroy(ev_decomp));
 
   // 5. assemble the PARTIAL aggregate batch
   int n_keys = (int)plan->group_cols.size();
@@ -3921,8 +3942,12 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
   bool empty_aggregate_row = (n_keys == 0 && nr == 0);
   if (empty_aggregate_row) { live.push_back(0); nr = 1; }
 
-  auto* ss = new StreamState();
+  // owned here until `out` takes it: a throw below frees the schema and the
+  // batch built so far through the stream's own release path
+  std::unique_ptr<StreamState, void (*)(StreamState*)> ss(new StreamState(),
+                                                          stream_state_free);
   memset(&ss->schema, 0, sizeof(ss->schema));
+  memset(&ss->batch, 0, sizeof(ss->batch));
   ss->schema.format = strdup("+s");
   ss->schema.name = strdup("");
   ss->schema.release = release_schema;
@@ -3970,14 +3995,13 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
     make_schema_field(ls->children[0], distinct_fmt(ai), "item");
   }
 
-  auto* eb = new ExportedBatch();
-  memset(&ss->batch, 0, sizeof(ss->batch));
   ss->batch.length = nr;
   ss->batch.n_buffers = 1;
   ss->batch.buffers = (const void**)calloc(1, sizeof(void*));
   ss->batch.n_children = n_fields;
   ss->batch.children = (struct ArrowArray**)calloc(n_fields, sizeof(void*));
   ss->batch.release = release_array;
+  auto* eb = new ExportedBatch();  // the batch owns it from the next line on
   ss->batch.private_data = eb;
 
   auto make_child = [&](int idx) {
@@ -3986,6 +4010,12 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
     ch->length = nr;
     ch->release = release_array;
     return ch;
+  };
+  // non-null count of aggregate i in the group whose table row starts at base
+  auto row_count = [&](size_t base, int i) -> uint64_t {
+    const auto& ap = plan->aggs[i];
+    return empty_aggregate_row
+               ? 0 : agg_count(table, base, i, ap.kind, ap.cnt_is_presence);
   };
 
   // decode combined gid -> per-key local gids
@@ -4013,9 +4043,7 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
   for (int64_t r = 0; r < nr; r++) {
     int64_t g = live[r];
     for (int k = n_keys - 1; k >= 0; k--) {
-      const auto& kc = plan->cols[plan->group_cols[k]];
       int32_t sz = (int32_t)key_card(plan->group_cols[k]);
-      (void)kc;
       key_gids[k][r] = (int32_t)(g % sz);
       g /= sz;
     }
@@ -4058,100 +4086,45 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
     for (size_t i2 = 0; i2 < need.size(); i2++) m[need[i2]] = std::move(strs[i2]);
   }
   f = 0;
+  // keys: bin start timestamps (ms), numeric key values from the claim
+  // table, utf8 from the global dictionary or (hash mode) the dec arena;
+  // the NULL group is gid 0
   for (int k = 0; k < n_keys; k++) {
     auto* ch = make_child(f++);
     auto& c = plan->cols[plan->group_cols[k]];
-    if (c.is_bin) {
-      // i64 key: the bin's start timestamp (ms)
-      ch->n_buffers = 2;
-      ch->buffers = (const void**)calloc(2, sizeof(void*));
-      int64_t* v = (int64_t*)eb->grab(nr * 8);
-      uint8_t* validity = (uint8_t*)eb->grab((nr + 7) / 8);
-      memset(validity, 0xff, (nr + 7) / 8);
-      int64_t nulls = 0;
-      for (int64_t r = 0; r < nr; r++) {
-        int32_t gid = key_gids[k][r];
-        if (gid > 0)
-          v[r] = c.bin_origin + (c.bin_min_idx + gid - 1) * c.bin_stride;
-        else {
-          v[r] = 0;
-          validity[r / 8] &= (uint8_t)~(1 << (r % 8));
-          nulls++;
-        }
-      }
-      if (nulls) { ch->buffers[0] = validity; ch->null_count = nulls; }
-      ch->buffers[1] = v;
-      continue;
-    }
-    if (c.numeric_key) {
-      // i64 key values from the claim table (NULL group at gid 0)
-      ch->n_buffers = 2;
-      ch->buffers = (const void**)calloc(2, sizeof(void*));
-      int64_t* v = (int64_t*)eb->grab(nr * 8);
-      uint8_t* validity = (uint8_t*)eb->grab((nr + 7) / 8);
-      memset(validity, 0xff, (nr + 7) / 8);
+    const auto& gids = key_gids[k];
+    if (c.is_bin || c.numeric_key) {
       const auto& g2k = num_keys[plan->group_cols[k]];
-      int64_t nulls = 0;
+      std::vector<int64_t> v(nr, 0);
+      std::vector<uint8_t> valid(nr, 0);
       for (int64_t r = 0; r < nr; r++) {
-        int32_t gid = key_gids[k][r];
-        if (gid > 0) {
-          v[r] = (int64_t)g2k[(size_t)gid - 1];
-        } else {
-          v[r] = 0;
-          validity[r / 8] &= (uint8_t)~(1 << (r % 8));
-          nulls++;
-        }
+        const int32_t gid = gids[r];
+        if (gid <= 0) continue;
+        valid[r] = 1;
+        v[r] = c.is_bin
+                   ? c.bin_origin + (c.bin_min_idx + gid - 1) * c.bin_stride
+                   : (int64_t)g2k[(size_t)gid - 1];
       }
-      if (nulls) { ch->buffers[0] = validity; ch->null_count = nulls; }
-      ch->buffers[1] = v;
+      set_i64_column(*eb, ch, v, &valid);
       continue;
     }
-    ch->n_buffers = 3;
-    ch->buffers = (const void**)calloc(3, sizeof(void*));
-    uint8_t* validity = (uint8_t*)eb->grab((nr + 7) / 8);
-    memset(validity, 0, (nr + 7) / 8);
-    int32_t* offs = (int32_t*)eb->grab((nr + 1) * 4);
-    auto key_str = [&](int32_t gid) -> const std::string& {
-      return c.hash_mode ? hash_names[plan->group_cols[k]][gid]
-                         : c.gdict[gid - 1];
-    };
-    size_t total = 0;
-    for (int64_t r = 0; r < nr; r++) {
-      int32_t gid = key_gids[k][r];
-      if (gid > 0) total += key_str(gid).size();
-    }
-    char* data = (char*)eb->grab(total);
-    size_t off = 0;
-    int64_t nulls = 0;
-    for (int64_t r = 0; r < nr; r++) {
-      offs[r] = (int32_t)off;
-      int32_t gid = key_gids[k][r];
-      if (gid > 0) {
-        validity[r / 8] |= (uint8_t)(1 << (r % 8));
-        const auto& s = key_str(gid);
-        memcpy(data + off, s.data(), s.size());
-        off += s.size();
-      } else nulls++;
-    }
-    offs[nr] = (int32_t)off;
-    ch->null_count = nulls;
-    ch->buffers[0] = nulls ? validity : nullptr;
-    ch->buffers[1] = offs;
-    ch->buffers[2] = data;
+    std::vector<const std::string*> strs(nr, nullptr);
+    for (int64_t r = 0; r < nr; r++)
+      if (gids[r] > 0)
+        strs[r] = c.hash_mode ? &hash_names[plan->group_cols[k]][gids[r]]
+                              : &c.gdict[gids[r] - 1];
+    set_utf8_column(*eb, ch, strs);
   }
   // presence
-  {
-    auto* ch = make_child(f++);
-    ch->n_buffers = 2;
-    ch->buffers = (const void**)calloc(2, sizeof(void*));
-    int64_t* v = (int64_t*)eb->grab(nr * 8);
-    for (int64_t r = 0; r < nr; r++)
-      v[r] = empty_aggregate_row ? 0 : (int64_t)table[(size_t)live[r] * slots];
-    ch->buffers[1] = v;
-  }
   int64_t rows_out_total = 0;
-  for (int64_t r = 0; r < nr; r++)
-    rows_out_total += empty_aggregate_row ? 0 : (int64_t)table[(size_t)live[r] * slots];
+  {
+    std::vector<int64_t> v(nr);
+    for (int64_t r = 0; r < nr; r++) {
+      v[r] = empty_aggregate_row ? 0 : (int64_t)table[(size_t)live[r] * slots];
+      rows_out_total += v[r];
+    }
+    set_i64_column(*eb, make_child(f++), v);
+  }
   // distinct aggs: row r owns the sorted pairs [doffs[r], doffs[r + 1]) —
   // list offsets and, by difference, the partition-local distinct counts
   std::vector<std::vector<int32_t>> doffs(n_distinct);
@@ -4168,147 +4141,70 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
     if (p != pr.size())
       throw std::runtime_error("count_distinct: pair outside the live groups");
   }
-  // aggs
+  // aggs: agg{i} then agg{i}_count
+  std::vector<int64_t> cnt(nr);
   for (int i = 0; i < n_aggs; i++) {
     auto* chv = make_child(f++);
-    int kind = plan->aggs[i].kind;
+    const auto& ap = plan->aggs[i];
+    const int kind = ap.kind;
     if (kind == AGGK_COUNT_DISTINCT) {
+      // both columns carry the partition-local distinct count
       size_t di = std::find(plan->distinct_aggs.begin(),
                             plan->distinct_aggs.end(), i) -
                   plan->distinct_aggs.begin();
-      auto* chc = make_child(f++);
-      for (auto* ch : {chv, chc}) {
-        ch->n_buffers = 2;
-        ch->buffers = (const void**)calloc(2, sizeof(void*));
-        int64_t* v = (int64_t*)eb->grab(nr * 8);
-        for (int64_t r = 0; r < nr; r++)
-          v[r] = doffs[di][r + 1] - doffs[di][r];
-        ch->buffers[1] = v;
-      }
+      for (int64_t r = 0; r < nr; r++)
+        cnt[r] = doffs[di][r + 1] - doffs[di][r];
+      set_i64_column(*eb, chv, cnt);
+      set_i64_column(*eb, make_child(f++), cnt);
       continue;
     }
-    bool is_rank = (kind == AGGK_MIN_RANK || kind == AGGK_MAX_RANK ||
-                    kind == AGGK_MIN_STR || kind == AGGK_MAX_STR);
-    uint8_t* validity = (uint8_t*)eb->grab((nr + 7) / 8);
-    memset(validity, 0xff, (nr + 7) / 8);
-    int64_t nulls = 0;
-    if (is_rank) {
-      // utf8 value column: rank -> dictionary string, or (hash mode)
-      // strref -> dec-arena bytes
-      const auto& c = plan->cols[plan->aggs[i].col_idx];
-      bool via_ref = (kind == AGGK_MIN_STR || kind == AGGK_MAX_STR);
-      std::vector<std::string> ref_strs;
+    for (int64_t r = 0; r < nr; r++)
+      cnt[r] = (int64_t)row_count((size_t)live[r] * slots, i);
+    if (kind == AGGK_MIN_STR || kind == AGGK_MAX_STR) {
+      // hash-mode utf8 min/max: strref -> dec-arena bytes
+      std::vector<uint64_t> refs;
       std::vector<int64_t> ref_rows;
-      if (via_ref) {
-        std::vector<uint64_t> refs;
-        for (int64_t r = 0; r < nr; r++) {
-          size_t base = (size_t)live[r] * slots;
-          uint64_t cnt = empty_aggregate_row ? 0
-                         : (plan->aggs[i].cnt_is_presence ? table[base]
-                                                          : table[base + 2 + 2 * i]);
-          uint64_t ref = table[base + 1 + 2 * i];
-          if (cnt && ref != ~0ull) { refs.push_back(ref); ref_rows.push_back(r); }
-        }
-        ref_strs = fetch_ref_strings(part, st, refs);
+      for (int64_t r = 0; r < nr; r++) {
+        uint64_t ref = table[(size_t)live[r] * slots + 1 + 2 * i];
+        if (cnt[r] && ref != ~0ull) { refs.push_back(ref); ref_rows.push_back(r); }
       }
-      chv->n_buffers = 3;
-      chv->buffers = (const void**)calloc(3, sizeof(void*));
-      int32_t* offs = (int32_t*)eb->grab((nr + 1) * 4);
-      size_t total = 0;
+      auto ref_strs = fetch_ref_strings(part, st, refs);
       std::vector<const std::string*> strs(nr, nullptr);
-      if (via_ref) {
-        for (size_t j = 0; j < ref_rows.size(); j++) {
-          strs[ref_rows[j]] = &ref_strs[j];
-          total += ref_strs[j].size();
-        }
-      } else
+      for (size_t j = 0; j < ref_rows.size(); j++)
+        strs[ref_rows[j]] = &ref_strs[j];
+      set_utf8_column(*eb, chv, strs);
+    } else if (kind == AGGK_MIN_RANK || kind == AGGK_MAX_RANK) {
+      // dict utf8 min/max: rank -> dictionary string
+      const auto& c = plan->cols[ap.col_idx];
+      std::vector<const std::string*> strs(nr, nullptr);
       for (int64_t r = 0; r < nr; r++) {
-        size_t base = (size_t)live[r] * slots;
-        uint64_t cnt = empty_aggregate_row ? 0
-                       : (plan->aggs[i].cnt_is_presence ? table[base]
-                                                        : table[base + 2 + 2 * i]);
-        if (cnt) {
-          int64_t rankv = (int64_t)table[base + 1 + 2 * i];
-          if (rankv >= 0 && rankv < (int64_t)c.rank_to_gid.size()) {
-            strs[r] = &c.gdict[(size_t)c.rank_to_gid[(size_t)rankv] - 1];
-            total += strs[r]->size();
-          }
-        }
+        if (!cnt[r]) continue;
+        int64_t rankv = (int64_t)table[(size_t)live[r] * slots + 1 + 2 * i];
+        if (rankv >= 0 && rankv < (int64_t)c.rank_to_gid.size())
+          strs[r] = &c.gdict[(size_t)c.rank_to_gid[(size_t)rankv] - 1];
       }
-      char* sdata = (char*)eb->grab(total);
-      size_t off = 0;
+      set_utf8_column(*eb, chv, strs);
+    } else {
+      std::vector<int64_t> vv(nr, 0);
+      std::vector<uint8_t> valid(nr, 1);
       for (int64_t r = 0; r < nr; r++) {
-        offs[r] = (int32_t)off;
-        if (strs[r]) {
-          memcpy(sdata + off, strs[r]->data(), strs[r]->size());
-          off += strs[r]->size();
+        if (kind == AGGK_COUNT_STAR || kind == AGGK_COUNT) {
+          vv[r] = cnt[r];
+        } else if (cnt[r] == 0) {
+          valid[r] = 0;
+        } else if (kind == AGGK_SUM_F64) {
+          // exact 256-bit superaccumulator, rounded once (acc256_to_double)
+          double d = acc256_to_double(
+              &fsums[((size_t)ap.fsum_idx * n_groups_exec +
+                      (size_t)live[r]) * 4]);
+          memcpy(&vv[r], &d, 8);
         } else {
-          validity[r / 8] &= (uint8_t)~(1 << (r % 8));
-          nulls++;
+          vv[r] = (int64_t)table[(size_t)live[r] * slots + 1 + 2 * i];
         }
       }
-      offs[nr] = (int32_t)off;
-      if (nulls) { chv->buffers[0] = validity; chv->null_count = nulls; }
-      chv->buffers[1] = offs;
-      chv->buffers[2] = sdata;
-      auto* chc2 = make_child(f++);
-      chc2->n_buffers = 2;
-      chc2->buffers = (const void**)calloc(2, sizeof(void*));
-      int64_t* cv2 = (int64_t*)eb->grab(nr * 8);
-      for (int64_t r = 0; r < nr; r++) {
-        size_t base = (size_t)live[r] * slots;
-        cv2[r] = empty_aggregate_row ? 0
-                 : (int64_t)(plan->aggs[i].cnt_is_presence
-                                 ? table[base] : table[base + 2 + 2 * i]);
-      }
-      chc2->buffers[1] = cv2;
-      continue;
+      set_i64_column(*eb, chv, vv, &valid);
     }
-    chv->n_buffers = 2;
-    chv->buffers = (const void**)calloc(2, sizeof(void*));
-    int64_t* vv = (int64_t*)eb->grab(nr * 8);
-    bool cip = plan->aggs[i].cnt_is_presence;
-    int fsi = plan->aggs[i].fsum_idx;
-    for (int64_t r = 0; r < nr; r++) {
-      size_t base = (size_t)live[r] * slots;
-      // count(*) == presence: k_agg no longer spends atomics on its slots;
-      // same for any agg whose column is footer-proven null-free
-      uint64_t cnt = empty_aggregate_row ? 0
-                     : ((kind == AGGK_COUNT_STAR || cip)
-                            ? table[base] : table[base + 2 + 2 * i]);
-      uint64_t val = empty_aggregate_row ? 0 : table[base + 1 + 2 * i];
-      if (kind == AGGK_COUNT_STAR || kind == AGGK_COUNT) {
-        vv[r] = (int64_t)cnt;
-      } else if (cnt == 0) {
-        vv[r] = 0;
-        validity[r / 8] &= (uint8_t)~(1 << (r % 8));
-        nulls++;
-      } else if (kind == AGGK_SUM_F64) {
-        // exact 256-bit superaccumulator, rounded once (acc256_to_double)
-        double d = acc256_to_double(
-            &fsums[((size_t)fsi * n_groups_exec + (size_t)live[r]) * 4]);
-        memcpy(&vv[r], &d, 8);
-      } else {
-        vv[r] = (int64_t)val;
-      }
-    }
-    if (nulls) {
-      chv->buffers[0] = validity;
-      chv->null_count = nulls;
-    }
-    chv->buffers[1] = vv;
-
-    auto* chc = make_child(f++);
-    chc->n_buffers = 2;
-    chc->buffers = (const void**)calloc(2, sizeof(void*));
-    int64_t* cv = (int64_t*)eb->grab(nr * 8);
-    for (int64_t r = 0; r < nr; r++) {
-      size_t base = (size_t)live[r] * slots;
-      cv[r] = empty_aggregate_row ? 0
-              : (int64_t)((kind == AGGK_COUNT_STAR || cip)
-                              ? table[base] : table[base + 2 + 2 * i]);
-    }
-    chc->buffers[1] = cv;
+    set_i64_column(*eb, make_child(f++), cnt);
   }
   // agg{i}_set: the partial state of a distinct agg — per row the list of
   // its distinct values, vgid resolved through the global dictionary (dict
@@ -4319,11 +4215,7 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
     const auto& pr = dpairs[di];
     const int64_t np = (int64_t)pr.size();
     auto* chl = make_child(f++);
-    chl->n_buffers = 2;
-    chl->buffers = (const void**)calloc(2, sizeof(void*));
-    int32_t* loffs = (int32_t*)eb->grab(((size_t)nr + 1) * 4);
-    memcpy(loffs, doffs[di].data(), ((size_t)nr + 1) * 4);
-    chl->buffers[1] = loffs;
+    set_list_offsets(*eb, chl, doffs[di]);
     chl->n_children = 1;
     chl->children = (struct ArrowArray**)calloc(1, sizeof(void*));
     auto* item = (struct ArrowArray*)calloc(1, sizeof(struct ArrowArray));
@@ -4339,11 +4231,9 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
     }
     auto vgid_of = [&](int64_t p) { return (size_t)(uint32_t)pr[(size_t)p]; };
     if (c.numeric_key) {
-      item->n_buffers = 2;
-      item->buffers = (const void**)calloc(2, sizeof(void*));
-      int64_t* v = (int64_t*)eb->grab((size_t)np * 8);
+      std::vector<int64_t> v((size_t)np);
       for (int64_t p = 0; p < np; p++) v[p] = (int64_t)g2r.at(vgid_of(p) - 1);
-      item->buffers[1] = v;
+      set_i64_column(*eb, item, v);
       continue;
     }
     std::vector<std::string> ref_strs;
@@ -4352,27 +4242,16 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
       for (int64_t p = 0; p < np; p++) refs[(size_t)p] = g2r.at(vgid_of(p) - 1);
       ref_strs = fetch_ref_strings(part, st, refs);
     }
-    auto str_of = [&](int64_t p) -> const std::string& {
-      return c.hash_mode ? ref_strs[(size_t)p] : c.gdict.at(vgid_of(p) - 1);
-    };
+    std::vector<const std::string*> strs((size_t)np);
     size_t total = 0;
-    for (int64_t p = 0; p < np; p++) total += str_of(p).size();
+    for (int64_t p = 0; p < np; p++) {
+      strs[p] = c.hash_mode ? &ref_strs[(size_t)p]
+                            : &c.gdict.at(vgid_of(p) - 1);
+      total += strs[p]->size();
+    }
     if (total > (size_t)INT32_MAX)
       throw std::runtime_error("count_distinct: set column beyond 2 GiB");
-    item->n_buffers = 3;
-    item->buffers = (const void**)calloc(3, sizeof(void*));
-    int32_t* soffs = (int32_t*)eb->grab(((size_t)np + 1) * 4);
-    char* sdata = (char*)eb->grab(total);
-    size_t off = 0;
-    for (int64_t p = 0; p < np; p++) {
-      soffs[p] = (int32_t)off;
-      const auto& s = str_of(p);
-      memcpy(sdata + off, s.data(), s.size());
-      off += s.size();
-    }
-    soffs[np] = (int32_t)off;
-    item->buffers[1] = soffs;
-    item->buffers[2] = sdata;
+    set_utf8_column(*eb, item, strs);
   }
 
   memset(out, 0, sizeof(*out));
@@ -4380,7 +4259,7 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
   out->get_next = ss_get_next;
   out->get_last_error = ss_get_last_error;
   out->release = ss_release;
-  out->private_data = ss;
+  out->private_data = ss.release();
 
   {
     std::lock_guard<std::mutex> g(plan->mu);

@@ -278,6 +278,57 @@ def test_reference_agrees_with_the_oracle(cs, i):
     assert_rows_equal(pc.ref_query(case, q), want, f"{name}: {q}")
 
 
+def test_hash_plain_length_wrap_is_refused(tmp_path, monkeypatch):
+    """A PLAIN byte-array page of a hash-mode column whose length field
+    would wrap 32-bit position arithmetic (pos + 4 + 0xFFFFFFFC == pos mod
+    2**32) must fail plan build instead of passing the overrun check and
+    handing bogus strrefs to the device. Plan building is pure host work
+    (GPUQ_FAKE_DEVICE)."""
+    import pyarrow as pa
+    import pyarrow.parquet as pq
+
+    from parseable_amd import GpuExecutionPlan, GpuqError, GpuSession
+
+    path = str(tmp_path / "wrap.parquet")
+    vals = ["aa", "bbb", "c"]
+    tbl = pa.table({
+        "p_timestamp": pa.array([pc.TS0 + i for i in range(3)],
+                                type=pa.timestamp("ms")),
+        "s": pa.array(vals, type=pa.string()),
+    })
+    pq.write_table(tbl, path, compression="none", use_dictionary=False,
+                   data_page_version="1.0", row_group_size=1 << 20)
+    # precondition: one v1 PLAIN data page, no dictionary — a dictionary-
+    # encoded page would let the plan build pass for nothing
+    assert pc.first_page_types(path)["s"] == ("BYTE_ARRAY", 0)
+    info = pc.inspect_file(path)["s"]
+    assert info["codec"] == "UNCOMPRESSED"
+    assert [p["encoding"] for p in info["pages"]] == ["PLAIN"]
+    assert info["values"] == vals
+
+    # the page's value block: after the page header and the def levels
+    rg = pq.ParquetFile(path).metadata.row_group(0)
+    cc = next(rg.column(i) for i in range(rg.num_columns)
+              if rg.column(i).path_in_schema == "s")
+    raw = bytearray(open(path, "rb").read())
+    ph, body = pc.thrift_struct(raw, cc.data_page_offset)
+    assert ph[2] == ph[3]                      # stored uncompressed
+    p = body
+    if info["optional"]:
+        p += 4 + int.from_bytes(raw[body:body + 4], "little")
+    assert raw[p:p + 6] == (2).to_bytes(4, "little") + b"aa"
+    second = p + 4 + len(vals[0])
+    assert raw[second:second + 4] == (3).to_bytes(4, "little")
+    raw[second:second + 4] = (0xFFFFFFFC).to_bytes(4, "little")
+    with open(path, "wb") as fh:
+        fh.write(raw)
+
+    monkeypatch.setenv("GPUQ_FAKE_DEVICE", "1")
+    q = {"select": [{"agg": "count_star"}], "group_by": ["s"]}
+    with pytest.raises(GpuqError, match="plain page overrun"):
+        GpuExecutionPlan(GpuSession(), [path], q).close()
+
+
 def test_refused_files_are_what_they_claim(tmp_path):
     """The files tests/test_gpu_pagecases.py expects plan build to refuse
     really hold BOOLEAN / FLOAT / FLBA / INT96 columns and a v2 data page."""
