@@ -117,8 +117,39 @@ typedef enum {
                          lit_kind/str/i64/f64 are ignored. Any decodable
                          column type (utf8, i64, i32, f64, timestamp); on a
                          required column it selects nothing */
-  GPUQ_IS_NOT_NULL    /* col IS NOT NULL (alerts_utils.rs:428-440); a no-op
+  GPUQ_IS_NOT_NULL,   /* col IS NOT NULL (alerts_utils.rs:428-440); a no-op
                          on a required column */
+  /* General patterns: col [NOT] LIKE / ILIKE 'pattern' ESCAPE '\'. Unlike
+   * the seven ops above, `str` is the SQL pattern AS WRITTEN:
+   *  - '%' matches any byte sequence, the empty one included; '_' matches
+   *    exactly one character: one byte plus every directly following byte in
+   *    0x80..0xBF — one code point on valid UTF-8, deterministic on any bytes;
+   *  - the escape character is always backslash (what the filter builder
+   *    emits, alerts_utils.rs:621-640, and the engine's default): it makes
+   *    the next character literal — \% \_ \\ and any other character too; a
+   *    lone trailing backslash is a plan-build error;
+   *  - the match is anchored at both ends: LIKE 'abc' is equality and
+   *    LIKE '' matches only the empty string (the empty LITERAL of CONTAINS
+   *    matches every non-null row instead);
+   *  - a NULL row satisfies none of the four, the negated ones included;
+   *  - ILIKE / NOT ILIKE fold ASCII 'A'-'Z' on both sides exactly like
+   *    GPUQ_ICONTAINS: the pattern's literal bytes are lower-cased at plan
+   *    build, a literal byte >= 0x80 in the pattern is a plan-build error,
+   *    haystack bytes >= 0x80 are never folded;
+   *  - the column must be utf8 and the literal GPUQ_LIT_STR, anything else
+   *    is a plan-build error;
+   *  - none of them prunes a file or a row group, or is elided by chunk
+   *    statistics;
+   *  - limits (plan-build errors): at most 255 literal-or-'_' elements and
+   *    at most 16 '%'-separated segments, counting the empty segment before
+   *    a leading and after a trailing '%' (consecutive '%' collapse);
+   *  - a pattern that is exactly '%lit%', 'lit%' or '%lit' without '_'
+   *    (ILIKE: '%lit%' only), or nothing but '%', builds the plan of the
+   *    matching op above. */
+  GPUQ_LIKE = 17,
+  GPUQ_NOT_LIKE,
+  GPUQ_ILIKE,
+  GPUQ_NOT_ILIKE
 } gpuq_op;
 
 typedef enum { GPUQ_LIT_I64 = 0, GPUQ_LIT_F64, GPUQ_LIT_STR } gpuq_lit;
@@ -390,6 +421,13 @@ enum { GPUQ_MASK_OR_RESET = 0, GPUQ_MASK_AND = 1 };
 int32_t gpuq_test_mask_ops(gpuq_ctx*, int32_t op, const uint8_t* a,
                            const uint8_t* b, int64_t n, int32_t a_lead,
                            int32_t b_lead, uint8_t* out_a, uint8_t* out_b);
+
+/* Compiles `pattern` (pattern_len bytes, GPUQ_LIKE syntax; fold != 0 for the
+ * ILIKE rules) and runs the matcher the kernels and the LUT build share on
+ * value[0, len). No canonicalisation, no device, no session. Returns 1 / 0,
+ * or -1 when the pattern does not compile. */
+int32_t gpuq_test_like_match(const char* pattern, uint32_t pattern_len,
+                             int32_t fold, const uint8_t* value, uint32_t len);
 
 #ifdef __cplusplus
 }

@@ -87,10 +87,14 @@ CODECS = {"uncompressed": 0, "snappy": 1, "lz4_raw": 7}
 OPS = {"eq": 0, "ne": 1, "lt": 2, "le": 3, "gt": 4, "ge": 5, "between": 6, "contains": 7,
        "icontains": 8, "starts_with": 9, "ends_with": 10, "not_contains": 11,
        "not_icontains": 12, "not_starts_with": 13, "not_ends_with": 14,
-       "is_null": 15, "is_not_null": 16}
+       "is_null": 15, "is_not_null": 16,
+       "like": 17, "not_like": 18, "ilike": 19, "not_ilike": 20}
 # the LIKE-family string ops and the literal-free null ops (include/gpuq.h)
 STR_OPS = ("contains", "icontains", "starts_with", "ends_with", "not_contains",
            "not_icontains", "not_starts_with", "not_ends_with")
+# general patterns: the literal is the SQL pattern as written ('%', '_',
+# backslash escape), not an unescaped byte string
+PATTERN_OPS = ("like", "not_like", "ilike", "not_ilike")
 NULL_OPS = ("is_null", "is_not_null")
 # gpuq_node_kind, and the query-IR keys of the two group kinds
 NODE_KINDS = {"leaf": 0, "and": 1, "or": 2}
@@ -168,6 +172,9 @@ def load():
         C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
         C.POINTER(GpuqDecompStats), C.POINTER(C.c_int32),
     ]
+    lib.gpuq_test_like_match.restype = C.c_int32
+    lib.gpuq_test_like_match.argtypes = [
+        C.c_char_p, C.c_uint32, C.c_int32, C.c_char_p, C.c_uint32]
     _lib = lib
     return lib
 
@@ -237,3 +244,12 @@ def mask_ops(session, op, a, b, a_lead=0, b_lead=0):
     if rc != 0:
         raise RuntimeError(lib.gpuq_last_error(session).decode(errors="replace"))
     return out_a.raw, out_b.raw
+
+
+def like_match(pattern: bytes, fold: bool, value: bytes) -> int:
+    """Test support: compile `pattern` (GPUQ_LIKE syntax; fold = the ILIKE
+    rules) and run the matcher the kernels share on `value`. 1 / 0, or -1 when
+    the pattern does not compile."""
+    return load().gpuq_test_like_match(bytes(pattern), len(pattern),
+                                       1 if fold else 0, bytes(value),
+                                       len(value))

@@ -109,8 +109,10 @@ Bound ts_window(const gpuq_pred* preds, const std::vector<int>& root_leaves) {
 // value in [min,max] match `op value`? can_be_pruned = !satisfy.
 bool stats_can_match(const JValue& stats, const gpuq_pred& p, int64_t lit_i,
                      double lit_f, const char* lit_s, int op) {
-  // LIKE family / IS [NOT] NULL: no min/max reasoning, never prune
-  if (op == GPUQ_CONTAINS || op >= GPUQ_ICONTAINS) return true;
+  // LIKE family / IS [NOT] NULL / general patterns (everything from
+  // GPUQ_ICONTAINS up to GPUQ_NOT_ILIKE): no min/max reasoning, never prune
+  if (op == GPUQ_CONTAINS || (op >= GPUQ_ICONTAINS && op <= GPUQ_NOT_ILIKE))
+    return true;
   // externally tagged serde enum: {"Int": {...}} | {"Float"} | {"String"} | {"Bool"}
   if (stats.has("Int")) {
     if (p.lit_kind != GPUQ_LIT_I64) return true;  // type mismatch: cannot prune
@@ -179,6 +181,8 @@ bool file_pruned(const JValue& fe, const gpuq_pred* preds,
     // either (manifest stats carry no null counts; a null op's literal
     // fields are undefined and must not reach stats_can_match)
     if (p.op >= GPUQ_ICONTAINS && p.op <= GPUQ_IS_NOT_NULL) return false;
+    // general LIKE / ILIKE patterns: a pattern bounds no min/max range
+    if (p.op >= GPUQ_LIKE && p.op <= GPUQ_NOT_ILIKE) return false;
     const JValue* st = find_stats(p.column);
     if (!st || st->kind != JValue::OBJ) return false;
     if (p.op == GPUQ_BETWEEN) {

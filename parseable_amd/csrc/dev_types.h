@@ -83,7 +83,9 @@ enum CmpMode { CMP_EQ = 0, CMP_NE, CMP_LT, CMP_LE, CMP_GT, CMP_GE, CMP_RANGE };
 // LIKE-family match mode: a StrKind with STRF_* flags or'ed on. FOLD lowers
 // ASCII 'A'-'Z' in the haystack (the needle arrives lower-cased from the
 // host); NEG flips the result for non-null rows only.
-enum StrKind { STR_CONTAINS = 0, STR_PREFIX = 1, STR_SUFFIX = 2 };
+// STR_PATTERN: a general LIKE / ILIKE pattern; the needle is then a compiled
+// LikePat (like.h), sizeof(LikePat) bytes, instead of literal bytes.
+enum StrKind { STR_CONTAINS = 0, STR_PREFIX = 1, STR_SUFFIX = 2, STR_PATTERN = 3 };
 enum { STRF_KIND = 3, STRF_FOLD = 4, STRF_NEG = 8 };
 // k_cmp_str takes one op: a CmpMode as is, or a LIKE-family match mode
 // tagged with a bit above both ranges. cmp_str_like_mode() undoes the tag

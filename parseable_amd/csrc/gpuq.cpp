@@ -15,6 +15,7 @@
 #include "meta.h"
 #include "kernels_api.h"
 #include "dev_types.h"
+#include "like.h"
 
 #include <hip/hip_runtime.h>
 #include <fcntl.h>
@@ -212,6 +213,11 @@ struct ColPlan {
 struct PredPlan {
   gpuq_pred p;
   std::string col, str_lit;
+  // the op as the caller gave it. A GPUQ_LIKE-family pattern that is one of
+  // the fixed shapes is rewritten at plan build: p.op becomes the existing op
+  // and str_lit its bare literal. A general pattern keeps its op, and str_lit
+  // holds the compiled LikePat (like.h) byte for byte.
+  int orig_op = 0;
 };
 
 struct AggPlan {
@@ -547,10 +553,13 @@ int find_or_add_col(std::vector<ColPlan>& cols, const std::string& name) {
   return (int)cols.size() - 1;
 }
 
-// LIKE family (CONTAINS and the seven ops added after it): utf8 only, routed
-// to the LUT / window / hash paths, never pruned or elided by min/max stats
+// LIKE family (CONTAINS, the seven ops added after it and the four general
+// pattern ops): utf8 only, routed to the LUT / window / hash paths, never
+// pruned or elided by min/max stats
+bool op_is_pattern(int op) { return op >= GPUQ_LIKE && op <= GPUQ_NOT_ILIKE; }
 bool op_is_like(int op) {
-  return op == GPUQ_CONTAINS || (op >= GPUQ_ICONTAINS && op <= GPUQ_NOT_ENDS_WITH);
+  return op == GPUQ_CONTAINS ||
+         (op >= GPUQ_ICONTAINS && op <= GPUQ_NOT_ENDS_WITH) || op_is_pattern(op);
 }
 bool op_is_null(int op) { return op == GPUQ_IS_NULL || op == GPUQ_IS_NOT_NULL; }
 // kernel match mode (dev_types.h StrKind | STRF_*) of a LIKE-family op
@@ -563,6 +572,10 @@ int like_mode(int op) {
     case GPUQ_NOT_ICONTAINS: return STR_CONTAINS | STRF_FOLD | STRF_NEG;
     case GPUQ_NOT_STARTS_WITH: return STR_PREFIX | STRF_NEG;
     case GPUQ_NOT_ENDS_WITH: return STR_SUFFIX | STRF_NEG;
+    case GPUQ_LIKE: return STR_PATTERN;
+    case GPUQ_NOT_LIKE: return STR_PATTERN | STRF_NEG;
+    case GPUQ_ILIKE: return STR_PATTERN | STRF_FOLD;
+    case GPUQ_NOT_ILIKE: return STR_PATTERN | STRF_FOLD | STRF_NEG;
     default: return STR_CONTAINS;
   }
 }
@@ -570,8 +583,9 @@ const char* op_name(int op) {
   static const char* names[] = {
       "eq", "ne", "lt", "le", "gt", "ge", "between", "contains", "icontains",
       "starts_with", "ends_with", "not_contains", "not_icontains",
-      "not_starts_with", "not_ends_with", "is_null", "is_not_null"};
-  return (op >= 0 && op <= GPUQ_IS_NOT_NULL) ? names[op] : "?";
+      "not_starts_with", "not_ends_with", "is_null", "is_not_null",
+      "like", "not_like", "ilike", "not_ilike"};
+  return (op >= 0 && op <= GPUQ_NOT_ILIKE) ? names[op] : "?";
 }
 
 // IS [NOT] NULL against one chunk's footer: null_count == 0 (or a required
@@ -669,6 +683,63 @@ bool pred_all_true(const gpuq_pred& p, const ColumnChunkMeta& cm,
   }
 }
 
+// GPUQ_LIKE family at plan build: compile the pattern, then either rewrite
+// the predicate to the existing op whose shape it has — so LIKE '%error%'
+// builds exactly the CONTAINS plan and runs in the tuned k_contains_win<>
+// kernel — or keep the op and carry the compiled LikePat in str_lit (the
+// needle pool uploads it like any literal).
+//   '%lit%'          -> [NOT_][I]CONTAINS lit
+//   'lit%' / '%lit'  -> [NOT_]STARTS_WITH / ENDS_WITH lit   (LIKE only)
+//   '%' ('%%', ..)   -> [NOT_]CONTAINS '': every non-null row, or none
+// Anything else is general: any '_', an inner '%', no '%' at all (not EQ: EQ
+// on a column with PLAIN pages forces hash mode, the window path does not),
+// and the ILIKE prefix / suffix shapes.
+void compile_pattern_pred(PredPlan& pp) {
+  const int op = pp.p.op;
+  const bool fold = op == GPUQ_ILIKE || op == GPUQ_NOT_ILIKE;
+  const bool neg = op == GPUQ_NOT_LIKE || op == GPUQ_NOT_ILIKE;
+  LikePat P;
+  if (const char* why = like_compile(pp.str_lit.data(), pp.str_lit.size(),
+                                     fold, &P)) {
+    const std::string w = why, name = op_name(op);
+    if (w == "non-ascii")  // the wording of the ICONTAINS rule
+      throw std::runtime_error(name + " literal must be ASCII "
+                               "(case folding is ASCII-only): " + pp.col);
+    if (w == "trailing backslash")
+      throw std::runtime_error(name + " pattern ends in a lone backslash: " +
+                               pp.col);
+    if (w == "too many elements")
+      throw std::runtime_error(name + " pattern has more than 255 elements: " +
+                               pp.col);
+    throw std::runtime_error(name + " pattern has more than 16 %-separated "
+                             "segments: " + pp.col);
+  }
+  std::string lit;
+  int as = -1;
+  switch (like_shape(P, &lit)) {
+    case LIKE_SHAPE_CONTAINS:
+      as = fold ? (neg ? GPUQ_NOT_ICONTAINS : GPUQ_ICONTAINS)
+                : (neg ? GPUQ_NOT_CONTAINS : GPUQ_CONTAINS);
+      break;
+    case LIKE_SHAPE_PREFIX:
+      if (!fold) as = neg ? GPUQ_NOT_STARTS_WITH : GPUQ_STARTS_WITH;
+      break;
+    case LIKE_SHAPE_SUFFIX:
+      if (!fold) as = neg ? GPUQ_NOT_ENDS_WITH : GPUQ_ENDS_WITH;
+      break;
+    case LIKE_SHAPE_ALL:
+      as = neg ? GPUQ_NOT_CONTAINS : GPUQ_CONTAINS;
+      break;
+    default: break;
+  }
+  if (as >= 0) {
+    pp.p.op = as;
+    pp.str_lit = lit;  // already lower-cased for the folding ops
+  } else {
+    pp.str_lit.assign(reinterpret_cast<const char*>(&P), sizeof(P));
+  }
+}
+
 // evaluate a string predicate against one dict entry (host; LUT build)
 bool eval_str_pred(const gpuq_pred& p, const std::string& lit,
                    const uint8_t* s, uint32_t len) {
@@ -679,7 +750,14 @@ bool eval_str_pred(const gpuq_pred& p, const std::string& lit,
     // NULL rows are zeroed by the expand mode, negated ops included.
     const int m = like_mode(p.op);
     bool ok = false;
-    if (lit.empty()) ok = true;
+    if ((m & STRF_KIND) == STR_PATTERN) {
+      // general pattern: `lit` is the compiled LikePat, matched by the one
+      // function the kernels call (like.h)
+      const LikePat& P = *reinterpret_cast<const LikePat*>(lit.data());
+      auto get = [&](uint32_t i) { return s[i]; };
+      ok = (m & STRF_FOLD) ? like_match<true>(P, get, len)
+                           : like_match<false>(P, get, len);
+    } else if (lit.empty()) ok = true;
     else if (len >= lit.size()) {
       const size_t nl = lit.size();
       auto fc = [&](uint8_t c) -> uint8_t {
@@ -1256,8 +1334,11 @@ void plan_debug_report(gpuq_plan* plan,
         }
         path = lut && win ? "lut+window" : win ? "window" : lut ? "lut" : "pruned";
       }
-      fprintf(stderr, "[gpuq plan] pred %zu col=%s op=%s path=%s\n", pi,
-              pp.col.c_str(), op_name(pp.p.op), path.c_str());
+      // op= is the op as given; a canonicalised pattern names the op it runs as
+      std::string as;
+      if (pp.orig_op != pp.p.op) as = std::string(" as=") + op_name(pp.p.op);
+      fprintf(stderr, "[gpuq plan] pred %zu col=%s op=%s path=%s%s\n", pi,
+              pp.col.c_str(), op_name(pp.orig_op), path.c_str(), as.c_str());
     } else if (op_is_null(pp.p.op)) {
       const auto& n = null_dbg[pi];
       static const char* nm[] = {"nulltask", "proven", "pruned"};
@@ -1281,8 +1362,9 @@ void plan_debug_report(gpuq_plan* plan,
       fprintf(stderr,
               "[gpuq plan] where pred %zu col=%s op=%s ctx=%d rowgroups: "
               "eval=%lld elided=%lld\n",
-              pi, plan->preds[pi].col.c_str(), op_name(plan->preds[pi].p.op),
-              plan->pred_ctx[pi], (long long)leaf_dbg[pi][0],
+              pi, plan->preds[pi].col.c_str(),
+              op_name(plan->preds[pi].orig_op), plan->pred_ctx[pi],
+              (long long)leaf_dbg[pi][0],
               (long long)leaf_dbg[pi][1]);
     for (size_t ni = 0; ni < plan->where.nodes.size(); ni++)
       if (plan->where.nodes[ni].kind == GPUQ_NODE_OR)
@@ -1346,8 +1428,9 @@ extern "C" gpuq_plan* gpuq_plan_build_where(
     PredPlan pp;
     pp.p = preds[i];
     pp.col = preds[i].column;
-    if (pp.p.op < GPUQ_EQ || pp.p.op > GPUQ_IS_NOT_NULL)
+    if (pp.p.op < GPUQ_EQ || pp.p.op > GPUQ_NOT_ILIKE)
       throw std::runtime_error("unknown predicate op on " + pp.col);
+    pp.orig_op = pp.p.op;
     // a null op carries no literal: its lit_kind/str/i64/f64 are not read
     if (!op_is_null(pp.p.op) && preds[i].str) pp.str_lit = preds[i].str;
     plan->preds.push_back(std::move(pp));
@@ -1440,6 +1523,9 @@ extern "C" gpuq_plan* gpuq_plan_build_where(
       c.null_preds.push_back((int)pi);
       continue;
     }
+    if (op_is_pattern(pp.p.op) && pp.p.lit_kind != GPUQ_LIT_STR)
+      throw std::runtime_error(std::string(op_name(pp.p.op)) +
+                               " needs a string literal: " + pp.col);
     if (op_is_like(pp.p.op) && pp.p.op != GPUQ_CONTAINS &&
         c.phys != PT_BYTE_ARRAY)
       throw std::runtime_error(std::string("string predicate ") +
@@ -1448,7 +1534,9 @@ extern "C" gpuq_plan* gpuq_plan_build_where(
     if (c.phys == PT_BYTE_ARRAY) {
       if (pp.p.lit_kind != GPUQ_LIT_STR)
         throw std::runtime_error("string column needs string literal: " + pp.col);
-      if (op_is_like(pp.p.op) && (like_mode(pp.p.op) & STRF_FOLD)) {
+      if (op_is_pattern(pp.p.op)) {
+        compile_pattern_pred(pp);
+      } else if (op_is_like(pp.p.op) && (like_mode(pp.p.op) & STRF_FOLD)) {
         // ASCII-only folding: lower-case the needle once here; a literal
         // with a byte >= 0x80 would need Unicode case mapping on both sides
         for (char& ch : pp.str_lit) {
@@ -4608,6 +4696,17 @@ extern "C" int32_t gpuq_test_decompress(
 // test support: the WHERE-tree mask-combine kernels on caller-supplied bytes
 // (include/gpuq.h gpuq_test_mask_ops)
 // ------------------------------------------------------------------
+// test support: like_compile + like_match (like.h) on one value — the very
+// function eval_str_pred, k_like_win<> and k_cmp_str call
+extern "C" int32_t gpuq_test_like_match(const char* pattern,
+                                        uint32_t pattern_len, int32_t fold,
+                                        const uint8_t* value, uint32_t len) {
+  LikePat P;
+  if (like_compile(pattern, pattern_len, fold != 0, &P)) return -1;
+  auto get = [&](uint32_t i) { return value[i]; };
+  return fold ? like_match<true>(P, get, len) : like_match<false>(P, get, len);
+}
+
 extern "C" int32_t gpuq_test_mask_ops(gpuq_ctx* ctx, int32_t op,
                                       const uint8_t* a, const uint8_t* b,
                                       int64_t n, int32_t a_lead,

@@ -18,6 +18,7 @@
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
 #include "dev_types.h"
+#include "like.h"
 #include "meta.h"
 
 namespace gpuq {
@@ -1564,7 +1565,15 @@ __global__ void k_cmp_str(const uint8_t* __restrict__ dec,
       const bool fold = (m & STRF_FOLD) != 0;
       auto hb = [&](uint8_t c) -> uint8_t { return fold ? fold1(c) : c; };
       ok = false;
-      if (lit_len == 0) ok = true;
+      if (kind == STR_PATTERN) {
+        // general pattern: lit is a compiled LikePat, matched by the shared
+        // matcher (like.h) straight from the arena; every read is bounded by
+        // len inside like_match
+        const LikePat& P = *reinterpret_cast<const LikePat*>(lit);
+        auto get = [&](uint32_t j) { return s[j]; };
+        ok = fold ? like_match<true>(P, get, len)
+                  : like_match<false>(P, get, len);
+      } else if (lit_len == 0) ok = true;
       else if (len >= lit_len) {
         if (kind == STR_CONTAINS) {
           const uint8_t c0 = lit[0];
@@ -2068,6 +2077,106 @@ k_affix_win(const uint8_t* __restrict__ dec,
       while (k < nlen && win[b + k] == needle[k]) k++;
       hit = (k == nlen);
     }
+    win_mask_and(mask, rowof, direct, row0, W.dense0 + i,
+                 (uint8_t)(hit ^ (neg != 0)));
+  }
+}
+
+// general LIKE / ILIKE patterns (inner '%', '_') over the same windows: the
+// block stages the window and the compiled pattern into LDS (threads index
+// the pattern divergently, so it must not sit in scalar / kernarg space),
+// then each thread runs like_match<FOLD> (like.h — the function the host LUT
+// build and k_cmp_str call) over its values through an LDS byte getter. The
+// matcher checks the bound before every byte it reads, so a short value
+// never reads into its neighbour. The LDS image stays exact (length
+// prefixes); FOLD folds haystack bytes at the compare.
+// A single oversized value (nbytes > CWIN) is matched in global memory: one
+// thread matches the head and tail segments, then every middle segment is
+// searched by the whole block — threads test strided start positions with
+// like_seg_fwd, the leftmost hit wins through an LDS atomicMin, and one
+// thread advances pos to the end of that match.
+template <bool FOLD>
+__global__ void __launch_bounds__(CTHREADS)
+k_like_win(const uint8_t* __restrict__ dec,
+           const DevCWin* __restrict__ wins, int n,
+           const DevPage* __restrict__ pages,
+           const uint16_t* __restrict__ starts_pool,
+           const uint8_t* __restrict__ pat, int /*plen*/, int neg,
+           const uint32_t* __restrict__ rowof, uint8_t* __restrict__ mask) {
+  __shared__ uint8_t win[CWIN];
+  __shared__ LikePat P;
+  __shared__ uint32_t s_pos, s_tail, s_best;
+  if (blockIdx.x >= (unsigned)n) return;
+  const DevCWin W = wins[blockIdx.x];
+  const DevPage pg = pages[W.page_id];
+  const uint32_t row0 = pg.row_start;
+  const bool direct = win_direct(pg, dec);
+  const uint8_t* src = dec + W.src;
+  for (uint32_t i = threadIdx.x; i < sizeof(LikePat); i += CTHREADS)
+    reinterpret_cast<uint8_t*>(&P)[i] = pat[i];
+  if (W.nbytes > CWIN) {  // single oversized value
+    uint32_t vl;
+    __builtin_memcpy(&vl, src, 4);
+    auto get = [&](uint32_t i) { return src[4 + i]; };
+    __syncthreads();  // P
+    if (threadIdx.x == 0) {
+      // head and tail; s_pos == LIKE_FAIL says the value cannot match
+      uint32_t pos = like_seg_fwd<FOLD>(P, 0, get, 0, vl), tail = vl;
+      if (P.n_seg == 1) {
+        if (pos != vl) pos = LIKE_FAIL;
+      } else if (pos != LIKE_FAIL) {
+        tail = like_seg_bwd<FOLD>(P, P.n_seg - 1u, get, vl);
+        if (tail == LIKE_FAIL || tail < pos) pos = LIKE_FAIL;
+      }
+      s_pos = pos;
+      s_tail = tail;
+      s_best = LIKE_FAIL;
+    }
+    __syncthreads();
+    const uint32_t tail = s_tail;
+    // s_pos / s_best are read after a barrier only, so every branch on them
+    // is block-uniform
+    for (uint32_t s = 1; s + 1 < P.n_seg; s++) {
+      const uint32_t pos = s_pos;
+      if (pos == LIKE_FAIL) break;
+      const uint32_t sl = P.seg_len[s];
+      // a start after tail - sl cannot match; stop once a start further left
+      // has hit
+      for (uint64_t q = (uint64_t)pos + threadIdx.x;
+           q + sl <= tail && q < *(volatile uint32_t*)&s_best; q += CTHREADS)
+        if (like_seg_fwd<FOLD>(P, s, get, (uint32_t)q, tail) != LIKE_FAIL) {
+          atomicMin(&s_best, (uint32_t)q);
+          break;
+        }
+      __syncthreads();
+      const uint32_t best = s_best;
+      __syncthreads();  // all have read s_best before it is reset
+      if (threadIdx.x == 0) {
+        s_pos = best == LIKE_FAIL ? LIKE_FAIL
+                                  : like_seg_fwd<FOLD>(P, s, get, best, tail);
+        s_best = LIKE_FAIL;
+      }
+      __syncthreads();
+    }
+    if (threadIdx.x == 0)
+      win_mask_and(mask, rowof, direct, row0, W.dense0,
+                   (uint8_t)((s_pos != LIKE_FAIL) ^ (neg != 0)));
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < CWIN / (CTHREADS * 4); k++) {
+    uint32_t p = threadIdx.x * 4u + (uint32_t)k * (CTHREADS * 4u);
+    uint32_t v;
+    __builtin_memcpy(&v, src + p, 4);
+    *(uint32_t*)&win[p] = v;
+  }
+  __syncthreads();
+  const uint32_t* win32 = (const uint32_t*)win;
+  for (uint32_t i = threadIdx.x; i < W.n_values; i += CTHREADS) {
+    const uint32_t o = starts_pool[W.starts + i];
+    const uint32_t vl = win_vlen(win32, o);
+    const uint8_t* v = win + o + 4;
+    const bool hit = like_match<FOLD>(P, [&](uint32_t j) { return v[j]; }, vl);
     win_mask_and(mask, rowof, direct, row0, W.dense0 + i,
                  (uint8_t)(hit ^ (neg != 0)));
   }
@@ -2866,6 +2975,10 @@ void launch_str_win(hipStream_t st, const uint8_t* dec, const DevCWin* wins,
   switch (mode & STRF_KIND) {
     case STR_PREFIX: launch(k_affix_win<false>, (int)neg); break;
     case STR_SUFFIX: launch(k_affix_win<true>, (int)neg); break;
+    case STR_PATTERN:  // needle = compiled LikePat, nlen = sizeof(LikePat)
+      if (fold) launch(k_like_win<true>, (int)neg);
+      else launch(k_like_win<false>, (int)neg);
+      break;
     default:
       if (fold && neg) launch(k_contains_win<true, true>);
       else if (fold) launch(k_contains_win<true, false>);

@@ -22,7 +22,8 @@ void launch_def_levels(hipStream_t, const uint8_t* dec, const DevPage*,
                        uint32_t* present, int32_t* d_err);
 // every LIKE-family mode over PLAIN-page windows (mode: StrKind | STRF_*,
 // dev_types.h): k_contains_win<FOLD, NEG> for the substring modes,
-// k_affix_win<SUFFIX> for prefix/suffix; a STRF_FOLD needle is lower-cased
+// k_affix_win<SUFFIX> for prefix/suffix, k_like_win<FOLD> for STR_PATTERN
+// (needle = a compiled LikePat, like.h); a STRF_FOLD needle is lower-cased
 void launch_str_win(hipStream_t, const uint8_t* dec, const DevCWin* wins,
                     int n, const DevPage* pages, const uint16_t* starts_pool,
                     const uint8_t* needle, int nlen, int mode,

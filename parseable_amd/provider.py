@@ -26,7 +26,8 @@ import json
 import os
 
 from . import _lib
-from ._lib import (AGGS, NODE_KINDS, NULL_OPS, OPS, STR_OPS, GpuqAgg, GpuqFile,
+from ._lib import (AGGS, NODE_KINDS, NULL_OPS, OPS, PATTERN_OPS, STR_OPS, GpuqAgg,
+                   GpuqFile,
                    GpuqMetrics, GpuqPred, GpuqWhereNode)
 
 
@@ -184,8 +185,9 @@ def _file_pruned(file_entry, preds):
         elif op == "ge":
             sat = mx >= value
         else:
-            # ne, the LIKE family and is_null/is_not_null: never pruned on
-            # min/max (reference does the same)
+            # ne, the LIKE family, the general patterns and
+            # is_null/is_not_null: never pruned on min/max (reference does
+            # the same)
             return False
         return not sat
 
@@ -200,7 +202,8 @@ def _file_pruned(file_entry, preds):
         if op == "between":
             return (check(col, "ge", p["lo"])
                     or check(col, "le" if not p.get("hi_exclusive") else "lt", p["hi"]))
-        if op == "ne" or op in STR_OPS or op in NULL_OPS:
+        if (op == "ne" or op in STR_OPS or op in PATTERN_OPS
+                or op in NULL_OPS):
             return False  # no literal to compare (null ops) / no min/max reasoning
         return check(col, op, p["lit"])
 
@@ -375,7 +378,7 @@ class StagingScanner:
                             else pc.less_equal(col, p["hi"]))
             elif op == "contains":
                 m = pc.match_substring(col, p["lit"])
-            elif op in STR_OPS:
+            elif op in STR_OPS or op in PATTERN_OPS:
                 m = _like_mask(col, op, p["lit"])
             elif op == "is_null":
                 m = pc.is_null(col)
@@ -535,6 +538,126 @@ class StagingScanner:
         return out
 
 
+_LIKE_MAX_ELEMS = 255
+_LIKE_MAX_SEGS = 16
+
+
+def _pattern_compile(op, pattern: bytes, fold: bool):
+    """GPUQ_LIKE pattern (include/gpuq.h) -> list of segments, each a list of
+    elements: an int literal byte, or None for '_'. The segments are the
+    pieces between runs of '%'; one segment means the pattern has no '%'.
+    Same escape rule, limits and errors as the native plan build."""
+    segs, cur, n_elem, i, last_pct = [], [], 0, 0, False
+    while i < len(pattern):
+        c = pattern[i]
+        i += 1
+        if c == 0x25 and last_pct:  # '%%' == '%'
+            continue
+        if c == 0x25:
+            segs.append(cur)
+            cur, last_pct = [], True
+            if len(segs) >= _LIKE_MAX_SEGS:
+                raise GpuqError(f"{op} pattern has more than 16 %-separated "
+                                "segments")
+            continue
+        last_pct = False
+        if c == 0x5C:  # backslash: the next byte is literal
+            if i >= len(pattern):
+                raise GpuqError(f"{op} pattern ends in a lone backslash")
+            c = pattern[i]
+            i += 1
+        elif c == 0x5F:
+            c = None
+        if c is not None and fold:
+            if c >= 0x80:
+                raise GpuqError(f"{op} literal must be ASCII "
+                                "(case folding is ASCII-only)")
+            if 0x41 <= c <= 0x5A:
+                c |= 0x20
+        n_elem += 1
+        if n_elem > _LIKE_MAX_ELEMS:
+            raise GpuqError(f"{op} pattern has more than 255 elements")
+        cur.append(c)
+    segs.append(cur)
+    return segs
+
+
+def _pattern_match(segs, v: bytes) -> bool:
+    """The native matcher (csrc/like.h) restated on bytes; `v` is already
+    ASCII-folded for the i-ops. Anchored, no backtracking: first segment
+    forward from 0, last segment backward from the end, each middle segment
+    at its leftmost match in between. '_' takes one byte plus the
+    continuation bytes (0x80..0xBF) directly after it."""
+    n = len(v)
+
+    def fwd(seg, pos, limit):
+        for e in seg:
+            if pos >= limit:
+                return -1
+            c = v[pos]
+            pos += 1
+            if e is None:
+                while pos < limit and (v[pos] & 0xC0) == 0x80:
+                    pos += 1
+            elif c != e:
+                return -1
+        return pos
+
+    def bwd(seg, p):
+        for e in reversed(seg):
+            if p == 0:
+                return -1
+            p -= 1
+            if e is None:
+                while p > 0 and (v[p] & 0xC0) == 0x80:
+                    p -= 1
+            elif v[p] != e:
+                return -1
+        return p
+
+    pos = fwd(segs[0], 0, n)
+    if len(segs) == 1:
+        return pos == n
+    if pos < 0:
+        return False
+    tail = bwd(segs[-1], n)
+    if tail < pos:  # covers the -1 of a failed tail match
+        return False
+    for seg in segs[1:-1]:
+        q = pos
+        while True:
+            if q + len(seg) > tail:
+                return False
+            end = fwd(seg, q, tail)
+            if end >= 0:
+                break
+            q += 1
+        pos = end
+    return True
+
+
+def _pattern_mask(col, op, lit):
+    """like / not_like / ilike / not_ilike on the staging leg: the pure-Python
+    matcher per distinct value (pc.match_like is Unicode-aware in '_' and in
+    case folding and would disagree with the GPU leg's byte rules)."""
+    import pyarrow as pa
+
+    if not isinstance(lit, str):
+        raise GpuqError(f"{op} needs a string literal")
+    neg = op.startswith("not_")
+    fold = op.endswith("ilike")
+    segs = _pattern_compile(op, lit.encode(), fold)
+    if isinstance(col, pa.ChunkedArray):
+        col = col.combine_chunks()
+    if not (pa.types.is_string(col.type) or pa.types.is_large_string(col.type)):
+        raise GpuqError(f"string predicate {op} on non-utf8 column")
+    enc = col.cast(pa.binary()).dictionary_encode()
+    lut = [_pattern_match(segs, v.lower() if fold else v) != neg
+           for v in enc.dictionary.to_pylist()]
+    # take() through the indices keeps NULL rows NULL (fill_null -> False)
+    return pa.array(lut, type=pa.bool_()).take(enc.indices)
+
+
 def _like_mask(col, op, lit):
     """LIKE-family predicate over a utf8 column on the staging leg, with the
     GPU leg's byte semantics (include/gpuq.h): the literal is a plain byte
@@ -542,9 +665,11 @@ def _like_mask(col, op, lit):
     the RE2 ignore_case are Unicode-aware and would disagree), a NULL row
     satisfies nothing — negated ops included — and an empty literal matches
     every non-null row (no row when negated). Evaluated once per distinct
-    value."""
+    value. The general pattern ops go through _pattern_mask."""
     import pyarrow as pa
 
+    if op in PATTERN_OPS:
+        return _pattern_mask(col, op, lit)
     if not isinstance(lit, str):
         raise GpuqError(f"string column needs string literal: {op}")
     neg = op.startswith("not_")
