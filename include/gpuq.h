@@ -284,6 +284,60 @@ gpuq_plan* gpuq_plan_build_from_stream_where(gpuq_ctx*, const char* stream_dir,
     int64_t* fast_count,
     const gpuq_where_node* nodes, int32_t n_nodes);
 
+/* Per-aggregate filter: agg(x) FILTER (WHERE f), the same thing as
+ * agg(CASE WHEN f THEN x END) — the spelling the reference's own SQL uses
+ * (SUM(CASE WHEN .. THEN 1 ELSE 0 END), MAX(CASE WHEN ..), COUNT(DISTINCT
+ * CASE WHEN .. END), handlers/http/traces.rs:492,560,591).
+ *  - a row contributes to aggregate `agg` iff the WHERE selection is 1 and
+ *    the filter tree is 1. The tree follows the rules of gpuq_where_node:
+ *    AND / OR groups, no NOT, node 0 the root with parent -1, a leaf 0 on a
+ *    NULL row (IS_NULL excepted); it combines 0/1 bytes, so three-valued
+ *    logic reduces to the leaf rule as for WHERE. A single LEAF node is a
+ *    one-pred filter. Normalisation is the WHERE tree's;
+ *  - groups are decided by WHERE alone: __presence counts WHERE-selected
+ *    rows, and a group whose rows all fail a filter stays in the result with
+ *    0 for count_star / count / count_distinct and NULL for sum / min / max
+ *    (and avg, its sum and count). With no group-by there is always one row;
+ *  - an aggregate without a filter behaves exactly as without this call;
+ *  - filter leaves never prune a file or a row group and never bound the
+ *    manifest time window, a p_timestamp leaf included; a query with any
+ *    filter never takes the manifest count fast path. Per-leaf chunk-stats
+ *    elision still applies inside a filter (proven rows keep the 1 their
+ *    buffer starts with);
+ *  - a filter on count_distinct builds the distinct set from the rows
+ *    passing WHERE and the filter;
+ *  - all leaves of WHERE and of every filter index the one `preds` array;
+ *    with n_nodes == 0 WHERE is the AND of the preds no filter uses;
+ *  - plan-build errors: a filter together with a projection; more than
+ *    MAX_AGGS (8) filters, `agg` out of range or two filters on one
+ *    aggregate; more than 32 leaves over WHERE and all filters together; an
+ *    OR depth above 4 in any one tree; a malformed filter tree (as for
+ *    WHERE); a pred used by two leaves anywhere, or by none.
+ * n_filters == 0 builds exactly the plan gpuq_plan_build_where builds. */
+typedef struct {
+  int32_t agg;                   /* index into aggs */
+  const gpuq_where_node* nodes;  /* a tree of its own: node 0 root, parent -1 */
+  int32_t n_nodes;               /* >= 1 */
+} gpuq_agg_filter;
+
+gpuq_plan* gpuq_plan_build_filtered(gpuq_ctx*,
+    const gpuq_file* files, int32_t n_files,
+    const char* const* projection, int32_t n_projection,
+    const gpuq_pred* preds, int32_t n_preds,
+    const char* const* group_by, int32_t n_group_by,
+    const gpuq_agg* aggs, int32_t n_aggs,
+    int64_t limit,
+    const gpuq_where_node* nodes, int32_t n_nodes,
+    const gpuq_agg_filter* filters, int32_t n_filters);
+gpuq_plan* gpuq_plan_build_from_stream_filtered(gpuq_ctx*, const char* stream_dir,
+    const char* const* projection, int32_t n_projection,
+    const gpuq_pred* preds, int32_t n_preds,
+    const char* const* group_by, int32_t n_group_by,
+    const gpuq_agg* aggs, int32_t n_aggs, int64_t limit,
+    int64_t* fast_count,
+    const gpuq_where_node* nodes, int32_t n_nodes,
+    const gpuq_agg_filter* filters, int32_t n_filters);
+
 /* Independent output partitions, one per selected device (the byte-balanced
  * row-group shards of balanced_file_groups, stream_schema_provider.rs:146-165,
  * collapsed to one stream per GPU). */

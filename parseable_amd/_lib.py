@@ -42,6 +42,12 @@ class GpuqAgg(C.Structure):
     _fields_ = [("op", C.c_int32), ("column", C.c_char_p)]
 
 
+class GpuqAggFilter(C.Structure):
+    """One aggregate's FILTER (WHERE ...) tree (gpuq_agg_filter)."""
+    _fields_ = [("agg", C.c_int32), ("nodes", C.POINTER(GpuqWhereNode)),
+                ("n_nodes", C.c_int32)]
+
+
 class GpuqMetrics(C.Structure):
     _fields_ = [
         ("rows_scanned", C.c_int64),
@@ -151,6 +157,15 @@ def load():
     lib.gpuq_plan_build_where.restype = C.c_void_p
     lib.gpuq_plan_build_where.argtypes = (
         lib.gpuq_plan_build.argtypes + [C.POINTER(GpuqWhereNode), C.c_int32])
+    # the *_filtered entry points: the *_where lists + (filters, n_filters)
+    lib.gpuq_plan_build_from_stream_filtered.restype = C.c_void_p
+    lib.gpuq_plan_build_from_stream_filtered.argtypes = (
+        lib.gpuq_plan_build_from_stream_where.argtypes
+        + [C.POINTER(GpuqAggFilter), C.c_int32])
+    lib.gpuq_plan_build_filtered.restype = C.c_void_p
+    lib.gpuq_plan_build_filtered.argtypes = (
+        lib.gpuq_plan_build_where.argtypes
+        + [C.POINTER(GpuqAggFilter), C.c_int32])
     lib.gpuq_test_mask_ops.restype = C.c_int32
     lib.gpuq_test_mask_ops.argtypes = [
         C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,

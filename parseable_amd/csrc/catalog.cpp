@@ -203,7 +203,10 @@ bool file_pruned(const JValue& fe, const gpuq_pred* preds,
 CatalogPlanInput catalog_plan(const std::string& stream_dir,
                               const gpuq_pred* preds, int32_t n_preds,
                               bool bare_count_star,
-                              const gpuq_where_node* nodes, int32_t n_nodes) {
+                              const gpuq_where_node* nodes, int32_t n_nodes,
+                              const gpuq_agg_filter* filters,
+                              int32_t n_filters, int32_t n_aggs,
+                              bool projection) {
   CatalogPlanInput out;
   std::string root = stream_dir;
   size_t slash = root.find_last_of('/');
@@ -212,14 +215,18 @@ CatalogPlanInput catalog_plan(const std::string& stream_dir,
   JPtr snap_doc = JsonParser(read_file(stream_dir + "/stream.json")).parse();
   const JValue& snapshot = snap_doc->at("snapshot");
   const JValue& mlist = snapshot.at("manifest_list");
-  const WhereTree tree = where_normalise(nodes, n_nodes, n_preds);
+  // only the WHERE tree is kept: filter leaves prune nothing and bound no
+  // window
+  const QueryTrees trees = where_normalise_filtered(
+      nodes, n_nodes, n_preds, filters, n_filters, n_aggs, projection);
+  const WhereTree& tree = trees.where;
   Bound win = ts_window(preds, tree.root_leaves);
 
   // value predicates excluding the window predicate itself (it is still a
   // pred for file-level ts pruning, so keep the full list for file_pruned)
   // — and any leaf below an OR counts as one, time leaves included: the
   // manifest sums cannot answer a disjunction
-  bool has_value_preds = !tree.conj;
+  bool has_value_preds = !tree.conj || n_filters > 0;
   for (int32_t i = 0; i < n_preds; i++)
     if (!preds[i].column || strcmp(preds[i].column, "p_timestamp") != 0 ||
         preds[i].op == GPUQ_IS_NULL || preds[i].op == GPUQ_IS_NOT_NULL)

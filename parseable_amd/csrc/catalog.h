@@ -22,11 +22,17 @@ struct CatalogPlanInput {
 // preds: the full conjunction including the injected time range
 // (a hi-exclusive BETWEEN on p_timestamp). nodes / n_nodes: the WHERE tree
 // over preds (where.h; n_nodes == 0 is the AND of all preds). Throws on
-// malformed metadata or a malformed tree.
+// malformed metadata or a malformed tree. filters: the aggregate filters
+// (gpuq_agg_filter), validated with the WHERE tree exactly as the scan
+// planner validates them; their leaves prune no file, bound no window and
+// keep the query off the count fast path.
 CatalogPlanInput catalog_plan(const std::string& stream_dir,
                               const gpuq_pred* preds, int32_t n_preds,
                               bool bare_count_star,
                               const gpuq_where_node* nodes = nullptr,
-                              int32_t n_nodes = 0);
+                              int32_t n_nodes = 0,
+                              const gpuq_agg_filter* filters = nullptr,
+                              int32_t n_filters = 0, int32_t n_aggs = 0,
+                              bool projection = false);
 
 }  // namespace gpuq

@@ -128,6 +128,10 @@ struct AggArgs {
   const uint8_t* agg_valid[MAX_AGGS];// may be null (= all valid)
   uint8_t cnt_skip[MAX_AGGS];        // footer null_count==0 for every chunk:
                                      // count == presence, skip count atomics
+  const uint8_t* agg_filter[MAX_AGGS];  // per-aggregate filter bytes (1 B/row),
+                                     // null = none: a selected row reaches
+                                     // agg i only where its byte is 1;
+                                     // presence never looks at it
   int32_t fsum_idx[MAX_AGGS];        // agg -> fsum table index (-1 = none)
   int32_t fsum_n;                    // number of f64-sum aggregates
   uint64_t* fsum;                    // superaccumulators (zeroed before launch)
@@ -149,6 +153,8 @@ struct DistinctArgs {
   const int32_t* key_gid[MAX_KEYS];
   int32_t key_size[MAX_KEYS];
   int32_t n_groups;             // bound on g (checked, ERR_DICT_RANGE)
+  const uint8_t* filter;        // the aggregate's filter bytes, null = none:
+                                // rows whose byte is 0 are skipped
   const int32_t* vgid;
   int32_t vcard;                // bound on vgid: cardinality incl. null slot
   uint64_t* pairs;              // out: claimed keys

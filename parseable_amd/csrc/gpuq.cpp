@@ -229,6 +229,7 @@ struct AggPlan {
   bool cnt_is_presence = false;  // every chunk's footer null_count == 0:
                                  // the non-null count IS the presence count
   int fsum_idx = -1;             // AGGK_SUM_F64 -> superaccumulator table idx
+  int filter = -1;               // index into gpuq_plan::filters, -1 = none
 };
 
 // one column chunk of one selected row group
@@ -324,6 +325,9 @@ struct Partition {
   int64_t* d_dictv = nullptr;
   uint8_t* d_lut = nullptr;
   uint8_t* d_mask = nullptr;
+  // one 1 B/row buffer per aggregate filter (gpuq_plan::filters), allocated
+  // at load only when the plan has filters
+  std::vector<uint8_t*> d_fbufs;
   // acc / tmp pairs of the non-folded OR groups, one pair per nesting level
   std::vector<uint8_t*> d_wbufs;
   int32_t* d_err = nullptr;
@@ -478,6 +482,16 @@ struct gpuq_plan {
   std::vector<WFold> wfolds;
   int n_wbufs = 0;
   int ctx_of(int pidx) const { return has_tree ? pred_ctx[pidx] : 0; }
+  bool no_fcount = false;  // GPUQ_NO_FCOUNT: k_agg<.., true> where k_agg_fcount
+                           // would run (A/B timing, tests)
+  // Aggregate filters (gpuq_agg_filter). Filter trees are appended to
+  // where.nodes as a forest (where_append) — where.root still spans WHERE
+  // alone, so pruning never sees a filter leaf — and each becomes one more
+  // context, evaluated into Partition::d_fbufs[j] after d_mask is final. A
+  // plan with filters always has has_tree set.
+  struct AggFilter { int agg; int root; int ctx; int depth; };
+  std::vector<AggFilter> filters;
+  std::vector<int> pred_filter;  // per pred: its filter, -1 for a WHERE leaf
   uint64_t distinct_bitmap_bits = DISTINCT_BITMAP_BITS;
   uint64_t distinct_lds_bits = DISTINCT_LDS_BITS;  // GPUQ_DISTINCT_LDS_BITS
   uint32_t distinct_pair_cap = DISTINCT_PAIR_CAP;
@@ -526,6 +540,7 @@ namespace {
 void read_env_knobs(gpuq_plan* plan) {
   plan->exec_dbg = getenv("GPUQ_PLAN_DEBUG") != nullptr;
   plan->no_fused_valagg = getenv("GPUQ_NO_FUSED_VALAGG") != nullptr;
+  plan->no_fcount = getenv("GPUQ_NO_FCOUNT") != nullptr;
   if (const char* e = getenv("GPUQ_VALAGG_BLOCKS"))
     plan->valagg_blocks = std::max(1, atoi(e));
   if (const char* e = getenv("GPUQ_DICT_WALK"))
@@ -1356,6 +1371,9 @@ void plan_debug_report(gpuq_plan* plan,
     fprintf(stderr, "[gpuq plan] where %s contexts=%zu depth=%d\n",
             where_expr(plan->where, plan->where.root).c_str(),
             plan->ctxs.size(), plan->where.depth);
+    for (const auto& f : plan->filters)
+      fprintf(stderr, "[gpuq plan] agg %d filter %s ctx=%d depth=%d\n", f.agg,
+              where_expr(plan->where, f.root).c_str(), f.ctx, f.depth);
     // per leaf: its mask context (-1: folded into a LUT) and how many row
     // groups evaluate it per row — elision holds inside an OR as well
     for (size_t pi = 0; pi < plan->preds.size(); pi++)
@@ -1393,7 +1411,21 @@ extern "C" gpuq_plan* gpuq_plan_build_where(
     const gpuq_pred* preds, int32_t n_preds,
     const char* const* group_by, int32_t n_group_by,
     const gpuq_agg* aggs, int32_t n_aggs, int64_t limit,
-    const gpuq_where_node* nodes, int32_t n_nodes) try {
+    const gpuq_where_node* nodes, int32_t n_nodes) {
+  return gpuq_plan_build_filtered(ctx, files, n_files, projection,
+                                  n_projection, preds, n_preds, group_by,
+                                  n_group_by, aggs, n_aggs, limit, nodes,
+                                  n_nodes, nullptr, 0);
+}
+
+extern "C" gpuq_plan* gpuq_plan_build_filtered(
+    gpuq_ctx* ctx, const gpuq_file* files, int32_t n_files,
+    const char* const* projection, int32_t n_projection,
+    const gpuq_pred* preds, int32_t n_preds,
+    const char* const* group_by, int32_t n_group_by,
+    const gpuq_agg* aggs, int32_t n_aggs, int64_t limit,
+    const gpuq_where_node* nodes, int32_t n_nodes,
+    const gpuq_agg_filter* filters, int32_t n_filters) try {
   (void)projection; (void)n_projection;
   auto plan = std::make_unique<gpuq_plan>();
   plan->ctx = ctx;
@@ -1437,11 +1469,27 @@ extern "C" gpuq_plan* gpuq_plan_build_where(
   }
   // WHERE tree: validated always; kept only when it is not a pure
   // conjunction, so such a tree builds exactly the flat plan
+  // Filter trees join the WHERE tree's node list as a forest; a plan with
+  // filters keeps its tree even when WHERE is a pure conjunction.
+  std::vector<int> filter_of_agg(std::max(n_aggs, 0), -1);
   {
-    WhereTree wt = where_normalise(nodes, n_nodes, n_preds);
-    if (!wt.conj) {
+    QueryTrees qt = where_normalise_filtered(nodes, n_nodes, n_preds, filters,
+                                             n_filters, n_aggs,
+                                             n_projection > 0);
+    if (!qt.where.conj || !qt.filters.empty()) {
       plan->has_tree = true;
-      plan->where = std::move(wt);
+      plan->where = std::move(qt.where);
+    }
+    plan->pred_filter.assign(plan->preds.size(), -1);
+    for (auto& ft : qt.filters) {
+      const int j = (int)plan->filters.size();
+      const int base = (int)plan->where.nodes.size();
+      const int root = where_append(plan->where, ft.tree);
+      for (size_t ni = base; ni < plan->where.nodes.size(); ni++)
+        if (plan->where.nodes[ni].kind == GPUQ_NODE_LEAF)
+          plan->pred_filter[plan->where.nodes[ni].pred] = j;
+      plan->filters.push_back({ft.agg, root, -1, ft.tree.depth});
+      filter_of_agg[ft.agg] = j;
     }
   }
   for (int32_t i = 0; i < n_group_by; i++) {
@@ -1470,6 +1518,7 @@ extern "C" gpuq_plan* gpuq_plan_build_where(
   for (int32_t i = 0; i < n_aggs; i++) {
     AggPlan ap;
     ap.op = aggs[i].op;
+    ap.filter = filter_of_agg[i];
     if (aggs[i].op == GPUQ_AGG_COUNT_DISTINCT) {
       if (!aggs[i].column)
         throw std::runtime_error("count_distinct needs a column");
@@ -1565,7 +1614,12 @@ extern "C" gpuq_plan* gpuq_plan_build_where(
   }
   // aggregate kinds
   for (auto& ap : plan->aggs) {
-    if (ap.op == GPUQ_AGG_COUNT_STAR) { ap.kind = AGGK_COUNT_STAR; continue; }
+    if (ap.op == GPUQ_AGG_COUNT_STAR) {
+      // a filtered count(*) is not the presence count: it counts into its own
+      // count slot, as a count over a column without a validity array does
+      ap.kind = ap.filter >= 0 ? AGGK_COUNT : AGGK_COUNT_STAR;
+      continue;
+    }
     auto& c = plan->cols[ap.col_idx];
     ap.is_f64 = (c.phys == PT_DOUBLE || c.phys == PT_FLOAT);
     if (ap.op == GPUQ_AGG_COUNT_DISTINCT) {
@@ -1867,6 +1921,13 @@ extern "C" gpuq_plan* gpuq_plan_build_where(
       }
     };
     assign(plan->where.root, 0, 0);
+    // one context per filter; its nested ORs reuse the level pairs of
+    // d_wbufs, trees being evaluated one after another
+    for (auto& f : plan->filters) {
+      f.ctx = (int)plan->ctxs.size();
+      plan->ctxs.emplace_back();
+      assign(f.root, f.ctx, 0);
+    }
   }
   // LUT slots per column: the contexts holding a LUT leaf or a folded group
   for (size_t ci = 0; ci < plan->cols.size(); ci++) {
@@ -2489,6 +2550,8 @@ extern "C" gpuq_plan* gpuq_plan_build_where(
   // engine gets from its statistics-based null handling).
   for (auto& ap : plan->aggs) {
     if (ap.op == GPUQ_AGG_COUNT_STAR || ap.col_idx < 0) continue;
+    // a filtered aggregate's count is not the presence count
+    if (ap.filter >= 0) continue;
     bool all0 = true;
     for (auto& part : plan->parts)
       for (auto& t : part.chunks)
@@ -2526,7 +2589,7 @@ extern "C" gpuq_plan* gpuq_plan_build_where(
     bool aggs_ok = true;
     for (auto& ap : plan->aggs) aggs_ok &= (ap.kind == AGGK_COUNT_STAR);
     plan->fused_count = plan->group_cols.size() == 1 && aggs_ok &&
-                        plan->preds.empty() && plan->n_groups <= 8192 &&
+                        plan->preds.empty() && plan->filters.empty() && plan->n_groups <= 8192 &&
                         !plan->cols[plan->group_cols[0]].is_bin &&
                         !plan->cols[plan->group_cols[0]].hash_mode &&
                         !plan->cols[plan->group_cols[0]].numeric_key;
@@ -2546,7 +2609,7 @@ extern "C" gpuq_plan* gpuq_plan_build_where(
   // takes with two aggregates, over a column that only the aggregate reads
   // and whose pages are all dict-encoded or PLAIN 8-byte
   if (!plan->is_projection && !plan->no_fused_valagg &&
-      plan->distinct_aggs.empty() &&
+      plan->distinct_aggs.empty() && plan->filters.empty() &&
       plan->group_cols.size() == 1 && plan->aggs.size() == 2 &&
       plan->aggs[0].kind == AGGK_COUNT_STAR && plan->n_fsum == 0 &&
       (plan->aggs[1].kind == AGGK_SUM_I64 || plan->aggs[1].kind == AGGK_MIN_I64 ||
@@ -2619,12 +2682,28 @@ extern "C" gpuq_plan* gpuq_plan_build_from_stream_where(
     const char* const* group_by, int32_t n_group_by,
     const gpuq_agg* aggs, int32_t n_aggs, int64_t limit,
     int64_t* fast_count,
-    const gpuq_where_node* nodes, int32_t n_nodes) try {
+    const gpuq_where_node* nodes, int32_t n_nodes) {
+  return gpuq_plan_build_from_stream_filtered(
+      ctx, stream_dir, projection, n_projection, preds, n_preds, group_by,
+      n_group_by, aggs, n_aggs, limit, fast_count, nodes, n_nodes, nullptr, 0);
+}
+
+extern "C" gpuq_plan* gpuq_plan_build_from_stream_filtered(
+    gpuq_ctx* ctx, const char* stream_dir,
+    const char* const* projection, int32_t n_projection,
+    const gpuq_pred* preds, int32_t n_preds,
+    const char* const* group_by, int32_t n_group_by,
+    const gpuq_agg* aggs, int32_t n_aggs, int64_t limit,
+    int64_t* fast_count,
+    const gpuq_where_node* nodes, int32_t n_nodes,
+    const gpuq_agg_filter* filters, int32_t n_filters) try {
   if (fast_count) *fast_count = -1;
+  // a filtered count(*) cannot be answered from num_rows
   bool bare = (n_aggs == 1 && aggs && aggs[0].op == GPUQ_AGG_COUNT_STAR &&
-               n_group_by == 0);
+               n_group_by == 0 && n_filters == 0);
   CatalogPlanInput in = catalog_plan(stream_dir, preds, n_preds, bare, nodes,
-                                     n_nodes);
+                                     n_nodes, filters, n_filters, n_aggs,
+                                     n_projection > 0);
   if (in.fast_count >= 0) {
     if (fast_count) *fast_count = in.fast_count;
     return nullptr;
@@ -2639,10 +2718,10 @@ extern "C" gpuq_plan* gpuq_plan_build_from_stream_where(
     files[i].row_groups = nullptr;
     files[i].n_row_groups = -1;
   }
-  gpuq_plan* plan = gpuq_plan_build_where(
+  gpuq_plan* plan = gpuq_plan_build_filtered(
       ctx, files.data(), (int32_t)files.size(), projection, n_projection,
       preds, n_preds, group_by, n_group_by, aggs, n_aggs, limit, nodes,
-      n_nodes);
+      n_nodes, filters, n_filters);
   // footer null counts can drop every row group of every kept file (IS NULL
   // on a required column): the empty relation, like an all-pruned file list
   bool null_pred = false;
@@ -2774,6 +2853,9 @@ extern "C" int32_t gpuq_plan_load(gpuq_plan* plan, int32_t pi) try {
   part.d_wbufs.assign(plan->n_wbufs, nullptr);
   for (auto& wb : part.d_wbufs)
     HIP_TRY(hipMalloc(&wb, std::max<int64_t>(part.n_rows, 16)));
+  part.d_fbufs.assign(plan->filters.size(), nullptr);
+  for (auto& fb : part.d_fbufs)
+    HIP_TRY(hipMalloc(&fb, std::max<int64_t>(part.n_rows, 16)));
   HIP_TRY(hipMalloc(&part.d_rowof, std::max<int64_t>(part.n_rows * 4, 16)));
   HIP_TRY(hipMalloc(&part.d_rank, std::max<int64_t>(part.n_rows * 4, 16)));
   HIP_TRY(hipMalloc(&part.d_scr, std::max<int64_t>(part.n_rows * 8, 16)));
@@ -3514,7 +3596,11 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
   // a query whose every predicate is chunk-stats-proven everywhere needs no
   // selection mask at all (string/contains preds are never elided, so their
   // presence keeps pred_ranges non-empty)
-  const bool need_mask = !plan->preds.empty() && !part.pred_ranges.empty();
+  // Filter leaves do not count: the WHERE mask may be absent while filter
+  // buffers exist.
+  bool need_mask = false;
+  for (const auto& pr : part.pred_ranges)
+    need_mask |= plan->pred_filter[pr.first] < 0;
   HIP_TRY(hipMemsetAsync(part.d_err, 0, 4, st));
   if (need_mask) HIP_TRY(hipMemsetAsync(part.d_mask, 1, part.n_rows, st));
   // group count with hash keys is only known after the hash build, so the
@@ -3781,8 +3867,13 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
   // k_mask_and folds acc into the parent's buffer. A term that is an AND
   // group evaluates all its leaves into the one buffer; a nested OR recurses
   // with the pair of the next level. d_mask is final after this block.
+  // Aggregate filters: each tree then evaluates the same way into a buffer
+  // of its own (set to 1 first), reusing the level pairs — every tmp buffer
+  // is all ones again when an OR group is done. A filter whose every leaf is
+  // chunk-stats-proven everywhere passes no buffer at all.
   int where_combines = 0;
-  if (plan->has_tree && need_mask) {
+  std::vector<const uint8_t*> fbuf(plan->filters.size(), nullptr);
+  if (plan->has_tree && (need_mask || !plan->filters.empty())) {
     for (size_t b = 1; b < part.d_wbufs.size(); b += 2)
       HIP_TRY(hipMemsetAsync(part.d_wbufs[b], 1, part.n_rows, st));
     std::function<void(int, uint8_t*)> eval_ors;
@@ -3808,7 +3899,16 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
         where_combines++;
       }
     };
-    eval_ors(0, part.d_mask);
+    if (need_mask) eval_ors(0, part.d_mask);
+    for (size_t j = 0; j < plan->filters.size(); j++) {
+      bool open = false;
+      for (const auto& pr : part.pred_ranges)
+        open |= plan->pred_filter[pr.first] == (int)j;
+      if (!open) continue;
+      HIP_TRY(hipMemsetAsync(part.d_fbufs[j], 1, part.n_rows, st));
+      eval_ctx(plan->filters[j].ctx, part.d_fbufs[j]);
+      fbuf[j] = part.d_fbufs[j];
+    }
   }
   if (plan->has_tree && plan->exec_dbg)
     fprintf(stderr, "[gpuq exec] part %d: where bufs=%zu combines=%d\n", (int)pi,
@@ -3880,6 +3980,7 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
     const auto& ap = plan->aggs[i];
     a.agg_kind[i] = ap.kind;
     a.cnt_skip[i] = ap.cnt_is_presence ? 1 : 0;
+    a.agg_filter[i] = ap.filter >= 0 ? fbuf[ap.filter] : nullptr;
     a.fsum_idx[i] = ap.fsum_idx;
     if (ap.col_idx >= 0) {
       auto itv = part.d_val.find(ap.col_idx);
@@ -3921,7 +4022,18 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
     if (plan->fused_valagg)
       for (auto& kv : part.tasks)
         if (kv.first.second == plan->valagg_col) run_task(kv, part.d_mask);
-    launch_agg(st, a);
+    const char* agg_path = launch_agg(st, a, plan->no_fcount);
+    if (plan->exec_dbg && !plan->filters.empty()) {
+      int live = 0;
+      for (auto* fb : fbuf) live += fb != nullptr;
+      fprintf(stderr,
+              "[gpuq exec] part %d: agg=%s filters=%zu filter_bufs=%d "
+              "n_groups=%lld table_bytes=%lld\n",
+              pi, agg_path, plan->filters.size(), live,
+              (long long)n_groups_exec,
+              (long long)((n_groups_exec * (1 + 2 * a.n_aggs) +
+                           (int64_t)a.fsum_n * n_groups_exec * 4) * 8));
+    }
   }
   // 3b. COUNT(DISTINCT): one set pass per distinct agg over the same final
   // masks and group index; the shared table is free again (cascade done)
@@ -3937,6 +4049,10 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
     }
     d.n_groups = (int32_t)n_groups_exec;
     d.vgid = part.d_gid[ci];
+    {
+      const int fj = plan->aggs[plan->distinct_aggs[di]].filter;
+      d.filter = fj >= 0 ? fbuf[fj] : nullptr;
+    }
     d.vcard = (int32_t)key_card(ci);
     d.pairs = part.d_dpairs[di];
     d.count = part.d_dcount + di;
@@ -4391,6 +4507,7 @@ gpuq_plan::~gpuq_plan() {
     F(part.d_raw); F(part.d_dec); F(part.d_pages); F(part.d_remap);
     F(part.d_dictv); F(part.d_lut); F(part.d_mask); F(part.d_err);
     for (auto* wb : part.d_wbufs) F(wb);
+    for (auto* fb : part.d_fbufs) F(fb);
     F(part.d_table); F(part.d_fsum); F(part.d_agg_kind);
     F(part.d_hkeys); F(part.d_hgids); F(part.d_hcount); F(part.d_cgid);
     for (auto& kv : part.d_gid2ref) F(kv.second);

@@ -1414,6 +1414,7 @@ __device__ __forceinline__ uint64_t look64(const uint64_t* p) {
 __device__ __forceinline__ bool distinct_key(const DistinctArgs& d, int64_t i,
                                              uint32_t& g, uint32_t& v) {
   if (d.mask && !d.mask[i]) return false;
+  if (d.filter && !d.filter[i]) return false;
   int32_t vg = d.vgid[i];
   if (vg == 0) return false;
   int64_t gg = 0;
@@ -2453,7 +2454,48 @@ __device__ inline void atomic_minmax_str(const uint8_t* dec, uint64_t* addr,
   }
 }
 
-template <bool USE_LDS>
+// one selected row `i` of group `g` into aggregate `ai` (kind k, neither
+// COUNT_STAR nor COUNT_DISTINCT): the per-aggregate body of k_agg, for its
+// filtered instantiations
+__device__ __forceinline__ void agg_update(const AggArgs& a, uint64_t* row,
+                                           uint64_t* fs, int ai, int k,
+                                           int32_t g, int64_t i) {
+  if (a.agg_valid[ai] && !a.agg_valid[ai][i]) return;
+  if (k == AGGK_COUNT) {
+    if (!a.cnt_skip[ai])
+      atomicAdd((unsigned long long*)&row[1 + 2 * ai + 1], 1ull);
+    return;
+  }
+  int64_t v = a.agg_val[ai][i];
+  uint64_t* vs = &row[1 + 2 * ai];
+  switch (k) {
+    case AGGK_SUM_I64: atomicAdd((unsigned long long*)vs, (unsigned long long)v); break;
+    case AGGK_SUM_F64: {
+      double d = __longlong_as_double((long long)v);
+      if (d != 0.0) {
+        uint64_t acc[4];
+        if (!acc256_decompose(d, acc)) {
+          if (a.err) atomicExch(a.err, ERR_FSUM_RANGE);
+        } else {
+          acc256_add(fs + ((int64_t)a.fsum_idx[ai] * a.n_groups + g) * 4, acc);
+        }
+      }
+      break;
+    }
+    case AGGK_MIN_I64: case AGGK_MIN_RANK: atomic_min_i64(vs, v); break;
+    case AGGK_MAX_I64: case AGGK_MAX_RANK: atomic_max_i64(vs, v); break;
+    case AGGK_MIN_F64: atomic_min_f64(vs, __longlong_as_double((long long)v)); break;
+    case AGGK_MAX_F64: atomic_max_f64(vs, __longlong_as_double((long long)v)); break;
+    case AGGK_MIN_STR: atomic_minmax_str(a.dec, vs, (uint64_t)v, true); break;
+    case AGGK_MAX_STR: atomic_minmax_str(a.dec, vs, (uint64_t)v, false); break;
+  }
+  if (!a.cnt_skip[ai])
+    atomicAdd((unsigned long long*)&row[1 + 2 * ai + 1], 1ull);
+}
+
+// FILT: some aggregate has a filter (AggArgs::agg_filter). The per-aggregate
+// test is compiled in only then; FILT = false is the kernel as it was.
+template <bool USE_LDS, bool FILT>
 __global__ void __launch_bounds__(256)
 k_agg(AggArgs a) {
   extern __shared__ uint64_t lt[];
@@ -2504,6 +2546,27 @@ k_agg(AggArgs a) {
       if (!((m4 >> (r * 8)) & 0xff)) { gs[r] = -1; continue; }
       for (int k = 0; k < a.n_keys; k++)
         gs[r] = gs[r] * a.key_size[k] + a.key_gid[k][i4 + r];
+    }
+    if (FILT) {
+      // presence first, whatever the filters say; then aggregate by
+      // aggregate, its four filter bytes in one load as m4 is. A row the
+      // WHERE mask dropped (gs < 0) never looks at its filter byte.
+#pragma unroll
+      for (int r = 0; r < 4; r++)
+        if (gs[r] >= 0)
+          atomicAdd((unsigned long long*)&tab[(int64_t)gs[r] * slots], 1ull);
+      for (int ai = 0; ai < a.n_aggs; ai++) {
+        int k = a.agg_kind[ai];
+        if (k == AGGK_COUNT_STAR || k == AGGK_COUNT_DISTINCT) continue;
+        uint32_t f4 = 0x01010101u;
+        if (a.agg_filter[ai]) __builtin_memcpy(&f4, a.agg_filter[ai] + i4, 4);
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          if (gs[r] < 0 || !((f4 >> (r * 8)) & 0xff)) continue;
+          agg_update(a, tab + (int64_t)gs[r] * slots, fs, ai, k, gs[r], i4 + r);
+        }
+      }
+      continue;
     }
 #pragma unroll
     for (int r = 0; r < 4; r++) {
@@ -2563,6 +2626,7 @@ k_agg(AggArgs a) {
       int k = a.agg_kind[ai];
       if (k == AGGK_COUNT_STAR) continue;  // == presence (export reads slot 0)
       if (k == AGGK_COUNT_DISTINCT) continue;  // the distinct-set pass counts it
+      if (FILT && a.agg_filter[ai] && !a.agg_filter[ai][i]) continue;
       if (a.agg_valid[ai] && !a.agg_valid[ai][i]) continue;
       if (k == AGGK_COUNT) {  // validity only; no value array needed
         if (!a.cnt_skip[ai])
@@ -2729,6 +2793,72 @@ k_agg_fast(AggArgs a) {
           atomic_max_i64(g, (int64_t)v);
         }
       }
+    }
+  }
+}
+
+// The error-rate shape: ONE key, every aggregate a count(*), at least one of
+// them filtered (count(*), count(*) FILTER (WHERE level = 'ERROR') BY host).
+// Per four rows: one 16 B gid load, 4 B of mask and 4 B per filter buffer;
+// mask and filter bytes are 0/1, so their AND says per row whether the
+// aggregate's count slot takes it. No kind dispatch, no validity or value
+// reads. An unfiltered count(*) is the presence slot, as in k_agg; table
+// layout and flush are k_agg's, so the export is untouched.
+template <bool USE_LDS>
+__global__ void __launch_bounds__(256)
+k_agg_fcount(AggArgs a) {
+  extern __shared__ uint64_t lt[];
+  const int slots = 1 + 2 * a.n_aggs;
+  const int64_t tsz = (int64_t)a.n_groups * slots;
+  uint64_t* tab;
+  if (USE_LDS) {
+    tab = lt;
+    for (int64_t i = threadIdx.x; i < tsz; i += blockDim.x) lt[i] = 0;
+    __syncthreads();
+  } else {
+    tab = a.table;  // count slots start at 0 (k_init_table)
+  }
+  const int32_t* __restrict__ gid = a.key_gid[0];
+  const int64_t tid0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t stride4 = (int64_t)gridDim.x * blockDim.x * 4;
+  const int64_t n4 = a.n_rows & ~3ll;
+  for (int64_t i4 = tid0 * 4; i4 < n4; i4 += stride4) {
+    uint32_t m4 = 0x01010101u;
+    if (a.mask) __builtin_memcpy(&m4, a.mask + i4, 4);
+    if (!m4) continue;
+    int32_t g4[4];
+    __builtin_memcpy(g4, gid + i4, 16);
+#pragma unroll
+    for (int r = 0; r < 4; r++)
+      if ((m4 >> (r * 8)) & 0xff)
+        atomicAdd((unsigned long long*)&tab[(int64_t)g4[r] * slots], 1ull);
+    for (int ai = 0; ai < a.n_aggs; ai++) {
+      if (a.agg_kind[ai] == AGGK_COUNT_STAR) continue;
+      uint32_t f4 = 0x01010101u;
+      if (a.agg_filter[ai]) __builtin_memcpy(&f4, a.agg_filter[ai] + i4, 4);
+      f4 &= m4;
+#pragma unroll
+      for (int r = 0; r < 4; r++)
+        if ((f4 >> (r * 8)) & 0xff)
+          atomicAdd((unsigned long long*)&tab[(int64_t)g4[r] * slots + 2 + 2 * ai],
+                    1ull);
+    }
+  }
+  for (int64_t i = n4 + tid0; i < a.n_rows; i += stride4 / 4) {
+    if (a.mask && !a.mask[i]) continue;
+    uint64_t* row = tab + (int64_t)gid[i] * slots;
+    atomicAdd((unsigned long long*)&row[0], 1ull);
+    for (int ai = 0; ai < a.n_aggs; ai++) {
+      if (a.agg_kind[ai] == AGGK_COUNT_STAR) continue;
+      if (a.agg_filter[ai] && !a.agg_filter[ai][i]) continue;
+      atomicAdd((unsigned long long*)&row[2 + 2 * ai], 1ull);
+    }
+  }
+  if (USE_LDS) {
+    __syncthreads();
+    for (int64_t t = threadIdx.x; t < tsz; t += blockDim.x) {
+      uint64_t v = tab[t];
+      if (v) atomicAdd((unsigned long long*)&a.table[t], (unsigned long long)v);
     }
   }
 }
@@ -3152,7 +3282,7 @@ void launch_val_agg(hipStream_t st, const uint8_t* dec, const DevPage* pages,
   }
 }
 
-void launch_agg(hipStream_t st, const AggArgs& a) {
+const char* launch_agg(hipStream_t st, const AggArgs& a, bool no_fcount) {
   size_t lds = ((size_t)a.n_groups * (1 + 2 * a.n_aggs) +
                 (size_t)a.fsum_n * a.n_groups * 4) * 8;
   int blocks = (int)((a.n_rows + 255) / 256);
@@ -3161,7 +3291,9 @@ void launch_agg(hipStream_t st, const AggArgs& a) {
   // fast path: one key, {COUNT_STAR [, one null-free i64 sum/min/max]}
   // (the c2 headline shape); validity reads and the per-agg dispatch
   // vanish, gid/val loads vectorize
-  bool fast = a.n_keys == 1 && a.n_aggs >= 1 && a.n_aggs <= 2 &&
+  bool filt = false;
+  for (int i = 0; i < a.n_aggs; i++) filt |= a.agg_filter[i] != nullptr;
+  bool fast = !filt && a.n_keys == 1 && a.n_aggs >= 1 && a.n_aggs <= 2 &&
               a.agg_kind[0] == AGGK_COUNT_STAR && a.fsum_n == 0;
   int k1 = AGGF_NONE;
   if (fast && a.n_aggs == 2) {
@@ -3192,13 +3324,35 @@ void launch_agg(hipStream_t st, const AggArgs& a) {
         default: launch(k_agg_fast<false, AGGF_NONE>); break;
       }
     }
-    return;
+    return "fast";
   }
-  if (use_lds) {
-    hipLaunchKernelGGL(k_agg<true>, dim3(blocks), dim3(256), lds, st, a);
+  if (filt && !no_fcount && a.n_keys == 1 && a.fsum_n == 0) {
+    // every aggregate a count(*): unfiltered (the presence slot) or filtered
+    // (AGGK_COUNT without a validity array, counting into its own slot)
+    bool counts = true;
+    for (int i = 0; i < a.n_aggs; i++)
+      counts &= a.agg_kind[i] == AGGK_COUNT_STAR ||
+                (a.agg_kind[i] == AGGK_COUNT && !a.agg_valid[i] &&
+                 !a.cnt_skip[i]);
+    if (counts) {
+      if (use_lds)
+        hipLaunchKernelGGL(k_agg_fcount<true>, dim3(blocks), dim3(256), lds, st, a);
+      else
+        hipLaunchKernelGGL(k_agg_fcount<false>, dim3(blocks), dim3(256), 0, st, a);
+      return "fcount";
+    }
+  }
+  if (filt) {
+    if (use_lds)
+      hipLaunchKernelGGL((k_agg<true, true>), dim3(blocks), dim3(256), lds, st, a);
+    else
+      hipLaunchKernelGGL((k_agg<false, true>), dim3(blocks), dim3(256), 0, st, a);
+  } else if (use_lds) {
+    hipLaunchKernelGGL((k_agg<true, false>), dim3(blocks), dim3(256), lds, st, a);
   } else {
-    hipLaunchKernelGGL(k_agg<false>, dim3(blocks), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((k_agg<false, false>), dim3(blocks), dim3(256), 0, st, a);
   }
+  return filt ? "general+filter" : "general";
 }
 
 void launch_pool_vals(hipStream_t st, const uint8_t* dec, const DevPage* pages,

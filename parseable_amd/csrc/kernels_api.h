@@ -84,7 +84,10 @@ void launch_val_agg(hipStream_t, const uint8_t* dec, const DevPage*,
                     const int32_t* gid, const uint8_t* mask, uint64_t* table,
                     int32_t n_groups, int n_aggs, int kind, int max_blocks,
                     bool serial_walk, int32_t* d_err);
-void launch_agg(hipStream_t, const AggArgs&);
+// -> the kernel family that ran: "fast", "general", and for a plan with
+// filters "fcount" (k_agg_fcount) or "general+filter" (k_agg<.., true>);
+// no_fcount keeps the error-rate shape on the general kernel
+const char* launch_agg(hipStream_t, const AggArgs&, bool no_fcount = false);
 void launch_pool_vals(hipStream_t, const uint8_t* dec, const DevPage*,
                       const int32_t* ids, int n, const int64_t* pool,
                       int64_t* out, uint8_t* valid, const uint32_t* present,

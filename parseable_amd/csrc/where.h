@@ -73,10 +73,14 @@ inline int or_depth(const WhereTree& t, int i) {
 }
 }  // namespace where_detail
 
-// n_nodes == 0: the AND of all preds. Throws std::runtime_error on every
-// malformed input (see gpuq_plan_build_where).
-inline WhereTree where_normalise(const gpuq_where_node* in, int32_t n_nodes,
-                                 int32_t n_preds) {
+namespace where_detail {
+// One tree of a query (the WHERE tree or an aggregate's filter tree): `used`
+// counts the leaves naming each pred and `leaves` the leaves seen, both
+// across all trees of the query. n_nodes == 0: the AND of the preds no tree
+// has used so far.
+inline WhereTree normalise_one(const gpuq_where_node* in, int32_t n_nodes,
+                               int32_t n_preds, std::vector<int>& used,
+                               int& leaves) {
   WhereTree t;
   if (n_nodes < 0 || (n_nodes > 0 && !in))
     throw std::runtime_error("where: bad node list");
@@ -84,19 +88,19 @@ inline WhereTree where_normalise(const gpuq_where_node* in, int32_t n_nodes,
     WNode r;
     r.kind = GPUQ_NODE_AND;
     for (int p = 0; p < n_preds; p++) {
+      if (used[p]++) continue;
       WNode l;
       l.pred = p;
       t.nodes.push_back(l);
-      r.kids.push_back(p);
+      r.kids.push_back((int)t.nodes.size() - 1);
       t.root_leaves.push_back(p);
+      leaves++;
     }
     t.nodes.push_back(r);
     t.root = (int)t.nodes.size() - 1;
     return t;
   }
   std::vector<std::vector<int>> kids(n_nodes);
-  std::vector<int> used(std::max(n_preds, 0), 0);
-  int leaves = 0;
   for (int i = 0; i < n_nodes; i++) {
     const auto& n = in[i];
     if (n.kind < GPUQ_NODE_LEAF || n.kind > GPUQ_NODE_OR)
@@ -125,10 +129,6 @@ inline WhereTree where_normalise(const gpuq_where_node* in, int32_t n_nodes,
       leaves++;
     }
   }
-  for (int p = 0; p < n_preds; p++)
-    if (!used[p])
-      throw std::runtime_error("where: predicate " + std::to_string(p) +
-                               " is used by no leaf");
   for (int i = 0; i < n_nodes; i++)
     if (in[i].kind != GPUQ_NODE_LEAF && kids[i].empty())
       throw std::runtime_error(
@@ -160,6 +160,88 @@ inline WhereTree where_normalise(const gpuq_where_node* in, int32_t n_nodes,
   if (t.depth > WHERE_MAX_OR_DEPTH)
     throw std::runtime_error("where: OR nesting depth above 4");
   return t;
+}
+inline void check_all_used(const std::vector<int>& used) {
+  for (size_t p = 0; p < used.size(); p++)
+    if (!used[p])
+      throw std::runtime_error("where: predicate " + std::to_string(p) +
+                               " is used by no leaf");
+}
+}  // namespace where_detail
+
+// n_nodes == 0: the AND of all preds. Throws std::runtime_error on every
+// malformed input (see gpuq_plan_build_where).
+inline WhereTree where_normalise(const gpuq_where_node* in, int32_t n_nodes,
+                                 int32_t n_preds) {
+  std::vector<int> used(std::max(n_preds, 0), 0);
+  int leaves = 0;
+  WhereTree t = where_detail::normalise_one(in, n_nodes, n_preds, used, leaves);
+  where_detail::check_all_used(used);
+  return t;
+}
+
+// A query's WHERE tree plus one filter tree per filtered aggregate
+// (gpuq_agg_filter): all leaves index the one preds array, every pred is
+// used by exactly one leaf of exactly one tree, and the 32-leaf cap holds
+// for all trees together. With n_nodes == 0 WHERE is the AND of the preds
+// no filter uses. Filter trees take the same normal form as WHERE.
+struct FilterTree { int agg = -1; WhereTree tree; };
+struct QueryTrees {
+  WhereTree where;
+  std::vector<FilterTree> filters;
+};
+inline QueryTrees where_normalise_filtered(
+    const gpuq_where_node* in, int32_t n_nodes, int32_t n_preds,
+    const gpuq_agg_filter* filters, int32_t n_filters, int32_t n_aggs,
+    bool projection) {
+  QueryTrees q;
+  if (n_filters < 0 || (n_filters > 0 && !filters))
+    throw std::runtime_error("filter: bad filter list");
+  if (n_filters > 0 && projection)
+    throw std::runtime_error(
+        "filter: an aggregate filter is not allowed in a projection plan");
+  std::vector<int> used(std::max(n_preds, 0), 0);
+  int leaves = 0;
+  if (n_nodes != 0)
+    q.where = where_detail::normalise_one(in, n_nodes, n_preds, used, leaves);
+  std::vector<char> seen(std::max(n_aggs, 0), 0);
+  for (int j = 0; j < n_filters; j++) {
+    const auto& f = filters[j];
+    if (f.agg < 0 || f.agg >= n_aggs)
+      throw std::runtime_error("filter " + std::to_string(j) +
+                               ": agg index out of range");
+    if (seen[f.agg]++)
+      throw std::runtime_error("filter " + std::to_string(j) +
+                               ": aggregate " + std::to_string(f.agg) +
+                               " already has a filter");
+    if (f.n_nodes < 1)
+      throw std::runtime_error("filter " + std::to_string(j) +
+                               ": a filter tree needs at least one node");
+    FilterTree ft;
+    ft.agg = f.agg;
+    ft.tree = where_detail::normalise_one(f.nodes, f.n_nodes, n_preds, used,
+                                          leaves);
+    q.filters.push_back(std::move(ft));
+  }
+  if (n_nodes == 0)
+    q.where = where_detail::normalise_one(nullptr, 0, n_preds, used, leaves);
+  if (n_filters > 0 && leaves > WHERE_MAX_LEAVES)
+    throw std::runtime_error("where: more than 32 leaves");
+  where_detail::check_all_used(used);
+  return q;
+}
+
+// Appends `src` to `dst.nodes` (a forest: nothing of dst refers to the new
+// nodes) and returns the index of src's root there. The planners' tree walks
+// (LUT folding, context assignment) then serve filter trees unchanged, while
+// everything that starts at dst.root — pruning above all — sees WHERE alone.
+inline int where_append(WhereTree& dst, const WhereTree& src) {
+  const int base = (int)dst.nodes.size();
+  for (WNode n : src.nodes) {
+    for (int& k : n.kids) k += base;
+    dst.nodes.push_back(std::move(n));
+  }
+  return base + src.root;
 }
 
 // Pruning as a tree evaluation. leaf_none(pred) says "no row of this file /

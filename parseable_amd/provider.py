@@ -28,7 +28,7 @@ import os
 from . import _lib
 from ._lib import (AGGS, NODE_KINDS, NULL_OPS, OPS, PATTERN_OPS, STR_OPS, GpuqAgg,
                    GpuqFile,
-                   GpuqMetrics, GpuqPred, GpuqWhereNode)
+                   GpuqAggFilter, GpuqMetrics, GpuqPred, GpuqWhereNode)
 
 
 class GpuqError(RuntimeError):
@@ -128,6 +128,22 @@ def _query_filter(query):
     if _where_is_conjunction(where):
         return flat + where_leaves(where), None
     return flat, where
+
+
+def agg_filters(query):
+    """[(agg index, filter tree)] of the aggregates of query["select"] that
+    carry a "filter" (agg(x) FILTER (WHERE f)): a leaf pred or a nested
+    {"and": [...]} / {"or": [...]} group, with the rules of `where`. Filters
+    restrict their aggregate alone: they never prune, never bound the time
+    window, and groups (and __presence) come from WHERE alone."""
+    out = []
+    for i, a in enumerate(query.get("select", [])):
+        f = a.get("filter")
+        if f is None:
+            continue
+        _check_groups(f)
+        out.append((i, f))
+    return out
 
 
 def _time_pred(tr):
@@ -354,6 +370,16 @@ class StagingScanner:
                           "lo": tr[0], "hi": tr[1], "hi_exclusive": True})
         if query.get("where") is not None:
             preds.append(query["where"])
+        mask = pa.array([True] * tbl.num_rows)
+        for p in preds:
+            mask = pc.and_(mask, StagingScanner._node_mask(tbl, p))
+        return mask
+
+    @staticmethod
+    def _node_mask(tbl, p):
+        """NULL-free boolean mask of one leaf pred or WHERE / filter group."""
+        import pyarrow as pa
+        import pyarrow.compute as pc
 
         def node_mask(p):
             # WHERE groups combine their children's NULL-free leaf masks
@@ -391,10 +417,7 @@ class StagingScanner:
                 m = f(col, p["lit"])
             return pc.fill_null(m, False)
 
-        mask = pa.array([True] * tbl.num_rows)
-        for p in preds:
-            mask = pc.and_(mask, node_mask(p))
-        return mask
+        return node_mask(p)
 
     def partial_batch(self, query):
         """-> pyarrow.RecordBatch in the partial-aggregate schema
@@ -409,10 +432,18 @@ class StagingScanner:
         aggs = query["select"]
         acc = {}
         set_types = {}
+        filters = dict(agg_filters(query))
+        if filters and query.get("select_cols"):
+            raise GpuqError("filter: an aggregate filter is not allowed in a "
+                            "projection plan")
         for tbl in self._tables():
-            sel = tbl.filter(self._mask(tbl, query))
+            mask = self._mask(tbl, query)
+            sel = tbl.filter(mask)
             if sel.num_rows == 0:
                 continue
+            # per filtered aggregate: its filter over the selected rows
+            fpass = {i: self._node_mask(tbl, f).filter(mask).to_pylist()
+                     for i, f in filters.items()}
             keys = []
             for g in group_by:
                 if isinstance(g, dict):  # DATE_BIN pseudo-key
@@ -459,6 +490,8 @@ class StagingScanner:
                     acc[key] = st
                 st[0] += 1
                 for i, a in enumerate(aggs):
+                    if i in fpass and not fpass[i][r]:
+                        continue
                     if a["agg"] == "count_star":
                         st[2][i] += 1
                         continue
@@ -882,6 +915,7 @@ class StandardTableProvider:
             and not query.get("select_cols")
             and len(sel) == 1
             and sel[0]["agg"] == "count_star"
+            and sel[0].get("filter") is None
         ):
             exact = True
             if time_range:
@@ -1009,11 +1043,51 @@ def _build_c_where(query: dict, keep):
     return cnodes, len(nodes)
 
 
+def _build_c_filters(query: dict, keep):
+    """-> (cfilters or None, n_filters) for the *_filtered entry points: one
+    gpuq_agg_filter per aggregate with a "filter", its leaves numbered after
+    all other preds in the order _build_c_query appends them. With filters
+    and a flat WHERE the node list of _build_c_where stays empty: WHERE is
+    then the AND of the preds no filter uses."""
+    filters = agg_filters(query)
+    if not filters:
+        return None, 0
+    flat, tree = _query_filter(query)
+    base = len(flat) + (1 if query.get("time_range") else 0)
+    if tree is not None:
+        base += len(where_leaves(tree))
+    cf = (GpuqAggFilter * len(filters))()
+    for j, (agg, f) in enumerate(filters):
+        nodes = []
+
+        def walk(node, parent):
+            nonlocal base
+            kind = _group_kind(node)
+            if kind is None:
+                nodes.append((NODE_KINDS["leaf"], parent, base))
+                base += 1
+                return
+            nodes.append((NODE_KINDS[kind], parent, -1))
+            me = len(nodes) - 1
+            for kid in node[kind]:
+                walk(kid, me)
+
+        walk(f, -1)
+        cn = (GpuqWhereNode * len(nodes))()
+        for i, (kind, parent, pred) in enumerate(nodes):
+            cn[i].kind, cn[i].parent, cn[i].pred = kind, parent, pred
+        keep.append(cn)
+        cf[j].agg, cf[j].nodes, cf[j].n_nodes = agg, cn, len(nodes)
+    keep.append(cf)
+    return cf, len(filters)
+
+
 def _build_c_query(query: dict, keep):
     """query IR -> (cpreds, n_preds, cgroup, n_group, caggs, n_aggs).
     `keep` collects byte strings that must outlive the C call. Pred order:
     the root conjuncts (preds, conjunct leaves of where), the time range,
-    then the leaves of an OR-bearing where tree depth first."""
+    then the leaves of an OR-bearing where tree depth first, then the leaves
+    of the aggregate filters in agg order, each depth first."""
     preds, tree = _query_filter(query)
     tr = query.get("time_range")
     if tr:
@@ -1021,6 +1095,9 @@ def _build_c_query(query: dict, keep):
                       "lo": tr[0], "hi": tr[1], "hi_exclusive": True})
     if tree is not None:
         preds, _ = _flatten_where(preds, tree)
+    # filter leaves follow all other preds, filter by filter, depth first
+    for _, f in agg_filters(query):
+        preds = preds + where_leaves(f)
     cpreds = (GpuqPred * max(len(preds), 1))()
     for i, p in enumerate(preds):
         b = p["col"].encode()
@@ -1085,15 +1162,19 @@ class GpuExecutionPlan:
         cpreds, np_, cgroup, ng, caggs, na = _build_c_query(query, self._keep)
         cproj, nproj, limit = _build_c_projection(query, self._keep)
         cnodes, nn = _build_c_where(query, self._keep)
+        cfilt, nf = _build_c_filters(query, self._keep)
         if stream_dir is not None:
             # native catalog planner (§8f row 1): manifest selection, pruning
             # and the count fast path run inside libgpuq (catalog.cpp)
             fc = C.c_int64(-1)
-            self._plan = lib.gpuq_plan_build_from_stream_where(
-                session._ctx, stream_dir.encode(),
-                cproj, nproj,
-                cpreds, np_, cgroup, ng, caggs, na,
-                C.c_int64(limit), C.byref(fc), cnodes, nn)
+            args = (session._ctx, stream_dir.encode(), cproj, nproj,
+                    cpreds, np_, cgroup, ng, caggs, na,
+                    C.c_int64(limit), C.byref(fc), cnodes, nn)
+            if nf:
+                self._plan = lib.gpuq_plan_build_from_stream_filtered(
+                    *args, cfilt, nf)
+            else:
+                self._plan = lib.gpuq_plan_build_from_stream_where(*args)
             if not self._plan:
                 if fc.value >= 0:
                     self.fast_count = fc.value
@@ -1111,16 +1192,12 @@ class GpuExecutionPlan:
             files[i].path = pb
             files[i].row_groups = None
             files[i].n_row_groups = -1
-        self._plan = lib.gpuq_plan_build_where(
-            session._ctx,
-            files, n,
-            cproj, nproj,
-            cpreds, np_,
-            cgroup, ng,
-            caggs, na,
-            C.c_int64(limit),
-            cnodes, nn,
-        )
+        args = (session._ctx, files, n, cproj, nproj, cpreds, np_,
+                cgroup, ng, caggs, na, C.c_int64(limit), cnodes, nn)
+        if nf:
+            self._plan = lib.gpuq_plan_build_filtered(*args, cfilt, nf)
+        else:
+            self._plan = lib.gpuq_plan_build_where(*args)
         if not self._plan:
             raise GpuqError(f"plan_build failed: {session._err()}")
         # footer null counts can drop every row group (is_null on a required
