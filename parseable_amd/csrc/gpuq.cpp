@@ -278,7 +278,41 @@ inline int tk_ctx(int kind, int ctx) { return kind | (ctx << TK_CTX_SHIFT); }
 inline int tk_kind(int key) { return key & ((1 << TK_CTX_SHIFT) - 1); }
 inline int tk_ctx_of(int key) { return key >> TK_CTX_SHIFT; }
 
-struct Partition {
+// decompress record vectors: what one planning unit (chunk) fills, and the
+// merged sets of a partition (launch_decompress consumes their device view)
+struct DecompRecs {
+  std::vector<DevSeg> segs;
+  std::vector<DevBr> brs;
+  std::vector<DevPageBr> pagebrs;
+  std::vector<DevBrRes> res_lane, res_wave;
+  std::vector<DevPiece> piece_pool;
+  std::vector<DevSeq> seqs;          // litpar sequence records ...
+  std::vector<DevSeqTile> tiles;     // ... and the tiles that own them
+  std::vector<DevLit> lits_wave;     // litpar literal runs > 256 B
+  // host-decompressed page images staged straight into the dec arena
+  // (snappy piece-explosion fallback — no serial snappy device kernel)
+  std::vector<std::pair<uint64_t, std::vector<uint8_t>>> himgs;
+};
+
+// device-side view of the decompress records, in launch order
+struct DecompDev {
+  const uint8_t* d_raw;
+  uint8_t* d_dec;
+  const DevSeg* d_segs; int n_segs;
+  const DevSeq* d_seqs;
+  const DevSeqTile* d_tiles; int n_tiles;
+  int seq_batch;   // tiles per block: 1 | 2 | 4 | 8
+  const DevLit* d_lits_wave; int n_lits_wave;
+  const DevBrRes* d_res_lane; int64_t n_res_lane;
+  const DevBrRes* d_res_wave; int n_res_wave;
+  const DevPiece* d_piece_pool;
+  const DevBr* d_brs;
+  const DevPageBr* d_pagebrs; int n_pagebrs;
+  int32_t* d_err;
+};
+
+// Partition's own DecompRecs base is the main record set (main stream).
+struct Partition : DecompRecs {
   int device = -1;
   std::vector<RgRef> rgs;
   int64_t n_rows = 0;
@@ -292,16 +326,11 @@ struct Partition {
   // LUT slots 1.. of the WHERE-tree contexts: pool j+1 has lut_pool's layout
   // (a page's aux_lut addresses every slot), zero where a column has fewer
   std::vector<std::vector<uint8_t>> lut_pool_x;
-  // segment-parallel LZ4 (host structure walk, meta.cpp lz4_walk)
-  std::vector<DevSeg> segs;
-  std::vector<DevBr> brs;            // deep/serial pages only (windowed wave)
-  std::vector<DevPageBr> pagebrs;
-  // literal-resolved records (single launch; meta.cpp lz4_walk)
-  std::vector<DevBrRes> res_lane, res_wave;
-  std::vector<DevPiece> piece_pool;
-  std::vector<DevSeq> seqs;          // litpar sequence records (dev_types.h)
-  std::vector<DevSeqTile> tiles;
-  std::vector<DevLit> lits_wave;     // litpar literal runs > 256 B
+  // Delta fork: columns whose decompress records, delta
+  // decode and comparisons run on the side stream, and the decompress
+  // records of their chunks, kept out of the main set
+  std::vector<int> fork_cols;
+  DecompRecs early;
   // contains windows (host length-chain walk at load time; dev_types.h)
   std::vector<DevCWin> cwins;
   std::vector<uint16_t> cstarts;
@@ -313,12 +342,12 @@ struct Partition {
   // per-pred row ranges still needing per-row evaluation (chunk-stats
   // elision, pred_all_true): merged-adjacent [start, start+len) pairs
   std::map<int, std::vector<std::pair<int64_t, int64_t>>> pred_ranges;
-  // host-decompressed page images -> dec arena at load (snappy fallback)
-  std::vector<std::pair<uint64_t, std::vector<uint8_t>>> himgs;
 
   // device state
   bool loaded = false;
   hipStream_t stream = nullptr;
+  hipStream_t side = nullptr;      // delta fork; only with fork_cols
+  DecompDev d_early{};             // device view of `early` (owned pointers)
   uint8_t *d_raw = nullptr, *d_dec = nullptr;
   DevPage* d_pages = nullptr;
   int32_t* d_remap = nullptr;
@@ -456,6 +485,9 @@ struct gpuq_plan {
   // dictionary-index decoders (kernels_api.h serial_walk), read at plan build:
   // GPUQ_DICT_WALK=serial forces the one-header-per-step walk
   bool dict_serial = false;
+  // sequence tiles per block (k_seq_tile<K>), GPUQ_SEQ_TILE_BATCH at build
+  int seq_tile_batch = SEQ_TILE_BATCH_DEFAULT;
+  bool no_delta_fork = false;    // GPUQ_NO_DELTA_FORK: serial order
   bool exec_dbg = false;         // GPUQ_PLAN_DEBUG at build: log the agg path
   // COUNT(DISTINCT) (read at plan build): aggs of that kind in agg order;
   // bitmap path when n_groups x padded value cardinality fits
@@ -536,6 +568,31 @@ extern "C" int32_t gpuq_device_count(void) {
 // ------------------------------------------------------------------
 namespace {
 
+// GPUQ_SEQ_TILE_BATCH=1|2|4|8: sequence tiles per block; anything else is
+// the default
+int seq_tile_batch_env() {
+  if (const char* e = getenv("GPUQ_SEQ_TILE_BATCH")) {
+    const int k = atoi(e);
+    if (k == 1 || k == 2 || k == 4 || k == 8) return k;
+  }
+  return SEQ_TILE_BATCH_DEFAULT;
+}
+
+// Delta fork, plan level: may column ci's decompress, decode and compare run
+// on the side stream? Only a column that nothing but numeric comparisons of
+// WHERE context 0 reads: no key, aggregate, distinct value, DATE_BIN source
+// or projection (val_always), no LUT / null predicate, no filter leaf.
+bool fork_col(const gpuq_plan& plan, int ci) {
+  const ColPlan& c = plan.cols[ci];
+  if (!c.need_val || c.val_always || c.need_gid || c.hash_mode ||
+      c.numeric_key || c.distinct_val || c.is_bin || c.cmp_preds.empty() ||
+      !c.lut_preds.empty() || !c.null_preds.empty())
+    return false;
+  for (int pidx : c.cmp_preds)
+    if (plan.ctx_of(pidx) != 0 || plan.pred_filter[pidx] >= 0) return false;
+  return true;
+}
+
 // environment knobs, read once into the plan
 void read_env_knobs(gpuq_plan* plan) {
   plan->exec_dbg = getenv("GPUQ_PLAN_DEBUG") != nullptr;
@@ -545,6 +602,8 @@ void read_env_knobs(gpuq_plan* plan) {
     plan->valagg_blocks = std::max(1, atoi(e));
   if (const char* e = getenv("GPUQ_DICT_WALK"))
     plan->dict_serial = strcmp(e, "serial") == 0;
+  plan->seq_tile_batch = seq_tile_batch_env();
+  plan->no_delta_fork = getenv("GPUQ_NO_DELTA_FORK") != nullptr;
   // COUNT(DISTINCT) knobs. The bitmap stays below 2^31 bits so the emit
   // pass's u32 list cursor cannot wrap; the pair cap can only be lowered.
   if (const char* e = getenv("GPUQ_DISTINCT_BITMAP_BITS"))
@@ -973,6 +1032,25 @@ std::vector<size_t> merge_stream(std::vector<C>& cbs, std::vector<T> B::*src,
   return merge_stream(cbs, src, dst, [](T&, size_t) {});
 }
 
+// the decompress record streams of every chunk, merged in chunk order
+template <class C>
+void merge_decomp_recs(std::vector<C>& cbs, DecompRecs& dst) {
+  merge_stream(cbs, &DecompRecs::segs, dst.segs);
+  const auto o_brs = merge_stream(cbs, &DecompRecs::brs, dst.brs);
+  merge_stream(cbs, &DecompRecs::pagebrs, dst.pagebrs,
+               [&](DevPageBr& pb, size_t i) { pb.start += (uint32_t)o_brs[i]; });
+  const auto o_pp = merge_stream(cbs, &DecompRecs::piece_pool, dst.piece_pool);
+  auto piece_rebase = [&](DevBrRes& r, size_t i) {
+    r.piece_start += (uint32_t)o_pp[i];
+  };
+  merge_stream(cbs, &DecompRecs::res_lane, dst.res_lane, piece_rebase);
+  merge_stream(cbs, &DecompRecs::res_wave, dst.res_wave, piece_rebase);
+  const auto o_sq = merge_stream(cbs, &DecompRecs::seqs, dst.seqs);
+  merge_stream(cbs, &DecompRecs::tiles, dst.tiles,
+               [&](DevSeqTile& t, size_t i) { t.rec0 += o_sq[i]; });
+  merge_stream(cbs, &DecompRecs::lits_wave, dst.lits_wave);
+}
+
 Ring::Ring(hipStream_t st) : stream(st) {
   for (int i = 0; i < NBUF; i++) {
     HIP_TRY(hipHostMalloc(&bufs[i], BUFSZ));
@@ -1027,21 +1105,6 @@ void Ring::copy(void* d_dst, const void* src, size_t len) {
 // page decompression planning + launches (shared by plan build / execute
 // and the gpuq_test_decompress test-support entry)
 // ------------------------------------------------------------------
-// device record vectors one planning unit (chunk) fills
-struct DecompRecs {
-  std::vector<DevSeg> segs;
-  std::vector<DevBr> brs;
-  std::vector<DevPageBr> pagebrs;
-  std::vector<DevBrRes> res_lane, res_wave;
-  std::vector<DevPiece> piece_pool;
-  std::vector<DevSeq> seqs;          // litpar sequence records ...
-  std::vector<DevSeqTile> tiles;     // ... and the tiles that own them
-  std::vector<DevLit> lits_wave;     // litpar literal runs > 256 B
-  // host-decompressed page images staged straight into the dec arena
-  // (snappy piece-explosion fallback — no serial snappy device kernel)
-  std::vector<std::pair<uint64_t, std::vector<uint8_t>>> himgs;
-};
-
 constexpr uint32_t BR_FAR = 16384 / 2;  // kernels.hip BR_WIN / 2
 
 // decompress planning for one page image (data or hash-col dict):
@@ -1257,28 +1320,13 @@ void plan_decomp_page(DecompRecs& cb, int codec, const uint8_t* praw,
   }
 }
 
-// device-side view of the decompress records, in launch order
-struct DecompDev {
-  const uint8_t* d_raw;
-  uint8_t* d_dec;
-  const DevSeg* d_segs; int n_segs;
-  const DevSeq* d_seqs;
-  const DevSeqTile* d_tiles; int n_tiles;
-  const DevLit* d_lits_wave; int n_lits_wave;
-  const DevBrRes* d_res_lane; int64_t n_res_lane;
-  const DevBrRes* d_res_wave; int n_res_wave;
-  const DevPiece* d_piece_pool;
-  const DevBr* d_brs;
-  const DevPageBr* d_pagebrs; int n_pagebrs;
-  int32_t* d_err;
-};
-
 // decompress: parallel segments, then ordered backref resolution
 void launch_decompress(hipStream_t st, const DecompDev& d) {
   launch_lz4_seg(st, d.d_raw, d.d_dec, d.d_segs, d.n_segs, d.d_err);
   // litpar pages: sequence tiles (short literals + inlined matches) and
   // flat long-literal copies, independent of the segment pass
-  launch_seq_tile(st, d.d_raw, d.d_dec, d.d_seqs, d.d_tiles, d.n_tiles);
+  launch_seq_tile(st, d.d_raw, d.d_dec, d.d_seqs, d.d_tiles, d.n_tiles,
+                  d.seq_batch);
   launch_lit_wave(st, d.d_raw, d.d_dec, d.d_lits_wave, d.n_lits_wave);
   // deferred-match resolution: host-resolved records are independent —
   // one launch each (kernel boundary after phase 1 gives coherence; their
@@ -1322,12 +1370,17 @@ void plan_debug_report(gpuq_plan* plan,
             "[gpuq plan] part %zu: rows=%lld chunks=%zu pages=%zu segs=%zu "
             "tiles=%zu tile_recs=%zu period_le3=%zu lits_wave=%zu "
             "res=%zu/%zu pieces=%zu raw=%.2fGB "
-            "dec=%.2fGB cwins=%zu\n",
+            "dec=%.2fGB cwins=%zu fork_cols=%zu early_segs=%zu "
+            "early_tiles=%zu early_tile_recs=%zu early_lits_wave=%zu "
+            "early_res=%zu/%zu early_pagebrs=%zu\n",
             p, (long long)pt.n_rows, pt.chunks.size(), pt.pages.size(),
             pt.segs.size(), pt.tiles.size(), pt.seqs.size(), period_le3,
             pt.lits_wave.size(), pt.res_lane.size(), pt.res_wave.size(),
             pt.piece_pool.size(), pt.raw_bytes / 1e9, pt.dec_bytes / 1e9,
-            pt.cwins.size());
+            pt.cwins.size(), pt.fork_cols.size(), pt.early.segs.size(),
+            pt.early.tiles.size(), pt.early.seqs.size(),
+            pt.early.lits_wave.size(), pt.early.res_lane.size(),
+            pt.early.res_wave.size(), pt.early.pagebrs.size());
   }
   // one line per string / null predicate: the path that evaluates it
   for (size_t pi = 0; pi < plan->preds.size(); pi++) {
@@ -2390,22 +2443,39 @@ extern "C" gpuq_plan* gpuq_plan_build_filtered(
     {
       const size_t nc = cbs.size();
       merge_stream(cbs, &CB::pages, part.pages);
-      merge_stream(cbs, &CB::segs, part.segs);
-      const auto o_brs = merge_stream(cbs, &CB::brs, part.brs);
-      merge_stream(cbs, &CB::pagebrs, part.pagebrs,
-                   [&](DevPageBr& pb, size_t i) {
-                     pb.start += (uint32_t)o_brs[i];
-                   });
-      const auto o_pp = merge_stream(cbs, &CB::piece_pool, part.piece_pool);
-      auto piece_rebase = [&](DevBrRes& r, size_t i) {
-        r.piece_start += (uint32_t)o_pp[i];
-      };
-      merge_stream(cbs, &CB::res_lane, part.res_lane, piece_rebase);
-      merge_stream(cbs, &CB::res_wave, part.res_wave, piece_rebase);
-      const auto o_sq = merge_stream(cbs, &CB::seqs, part.seqs);
-      merge_stream(cbs, &CB::tiles, part.tiles,
-                   [&](DevSeqTile& t, size_t i) { t.rec0 += o_sq[i]; });
-      merge_stream(cbs, &CB::lits_wave, part.lits_wave);
+      // Delta fork: a column forks when the plan allows it (fork_col) and
+      // every chunk of it that is decoded here is DELTA_BINARY_PACKED
+      // throughout, so its only value task is TK_DELTA_VAL, which touches
+      // none of decode_values' shared scratch. The decompress records of
+      // those chunks move to the early set; host-staged images stay with
+      // the main set (they are uploaded at load, not launched).
+      std::vector<DecompRecs> ecbs(nc);
+      if (!plan->no_delta_fork) {
+        std::vector<char> forks(plan->cols.size(), 0), seen = forks;
+        for (size_t ci = 0; ci < plan->cols.size(); ci++)
+          forks[ci] = fork_col(*plan, (int)ci);
+        for (size_t i = 0; i < nc; i++) {
+          const auto& t = part.chunks[i];
+          if (!forks[t.col_idx] || !stubs[i].need_val_decode) continue;
+          seen[t.col_idx] = 1;
+          for (const auto& pi : t.pages)
+            if (pi.type == PAGE_DATA && pi.encoding != ENC_DELTA_BP)
+              forks[t.col_idx] = 0;
+        }
+        for (size_t ci = 0; ci < plan->cols.size(); ci++)
+          if (forks[ci] && seen[ci]) part.fork_cols.push_back((int)ci);
+        for (size_t i = 0; i < nc; i++) {
+          const int ci = part.chunks[i].col_idx;
+          if (!forks[ci] || !seen[ci] || !stubs[i].need_val_decode) continue;
+          DecompRecs& all = cbs[i];
+          auto himgs = std::move(all.himgs);
+          ecbs[i] = std::move(all);
+          all = DecompRecs{};
+          all.himgs = std::move(himgs);
+        }
+      }
+      merge_decomp_recs(cbs, part);
+      merge_decomp_recs(ecbs, part.early);
       // small, order-sensitive leftovers stay serial
       for (size_t i = 0; i < nc; i++) {
         auto& cb = cbs[i];
@@ -2751,6 +2821,10 @@ extern "C" int32_t gpuq_plan_load(gpuq_plan* plan, int32_t pi) try {
   int64_t t0 = now_ns();
   HIP_TRY(hipSetDevice(part.device));
   HIP_TRY(hipStreamCreateWithFlags(&part.stream, hipStreamNonBlocking));
+  // the side stream of the delta fork, for partitions that have one: an
+  // idle second stream is not free (§7: +0.2 ms of host time per step)
+  if (!part.fork_cols.empty())
+    HIP_TRY(hipStreamCreateWithFlags(&part.side, hipStreamNonBlocking));
 
   // slack: the LZ4 input-window refill may read up to LZ4_IN+256 past the
   // last chunk's end (see kernels.hip refill note)
@@ -2946,6 +3020,24 @@ extern "C" int32_t gpuq_plan_load(gpuq_plan* plan, int32_t pi) try {
               (void**)&part.d_tiles);
   upload_pool(part.lits_wave.data(), part.lits_wave.size() * sizeof(DevLit),
               (void**)&part.d_lits_wave);
+  if (!part.fork_cols.empty()) {
+    // the early record set (delta fork), same shape as the main one
+    const DecompRecs& E = part.early;
+    DecompDev& D = part.d_early;
+    auto up = [&](const auto& v, auto** dst) {
+      upload_pool(v.data(), v.size() * sizeof(v[0]), (void**)dst);
+    };
+    up(E.segs, &D.d_segs); D.n_segs = (int)E.segs.size();
+    up(E.seqs, &D.d_seqs);
+    up(E.tiles, &D.d_tiles); D.n_tiles = (int)E.tiles.size();
+    up(E.lits_wave, &D.d_lits_wave); D.n_lits_wave = (int)E.lits_wave.size();
+    up(E.res_lane, &D.d_res_lane); D.n_res_lane = (int64_t)E.res_lane.size();
+    up(E.res_wave, &D.d_res_wave); D.n_res_wave = (int)E.res_wave.size();
+    up(E.piece_pool, &D.d_piece_pool);
+    up(E.brs, &D.d_brs);
+    up(E.pagebrs, &D.d_pagebrs); D.n_pagebrs = (int)E.pagebrs.size();
+    D.seq_batch = plan->seq_tile_batch;
+  }
   upload_pool(part.cwins.data(), part.cwins.size() * sizeof(DevCWin),
               (void**)&part.d_cwins);
   upload_pool(part.cstarts.data(), part.cstarts.size() * sizeof(uint16_t),
@@ -3354,9 +3446,15 @@ int proj_get_next(struct ArrowArrayStream* st0, struct ArrowArray* out) try {
 
 }  // namespace
 
-// The three events of one execute: created at entry, destroyed on every exit.
+// The events of one execute: created at entry, destroyed on every exit.
+// A delta fork in flight is part of that state: fork_side() starts the side
+// stream behind the main stream's work so far, join_side() makes the main
+// stream wait for it, and an exit between the two (a throw) drains the side
+// stream first, so no launch outlives the call.
 struct ExecEvents {
   hipEvent_t ev0 = nullptr, ev1 = nullptr, decomp = nullptr;
+  hipEvent_t fork = nullptr, join = nullptr;
+  hipStream_t side = nullptr;   // non-null between fork_side and join_side
   ExecEvents() = default;
   ExecEvents(const ExecEvents&) = delete;
   ExecEvents& operator=(const ExecEvents&) = delete;
@@ -3365,8 +3463,22 @@ struct ExecEvents {
     HIP_TRY(hipEventCreate(&ev1));
     HIP_TRY(hipEventCreate(&decomp));
   }
+  void fork_side(hipStream_t main, hipStream_t sd) {
+    HIP_TRY(hipEventCreateWithFlags(&fork, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&join, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(fork, main));
+    HIP_TRY(hipStreamWaitEvent(sd, fork, 0));
+    side = sd;
+  }
+  void join_side(hipStream_t main) {
+    if (!side) return;
+    HIP_TRY(hipEventRecord(join, side));
+    HIP_TRY(hipStreamWaitEvent(main, join, 0));
+    side = nullptr;
+  }
   ~ExecEvents() {
-    for (hipEvent_t e : {ev0, ev1, decomp})
+    if (side) (void)hipStreamSynchronize(side);
+    for (hipEvent_t e : {ev0, ev1, decomp, fork, join})
       if (e) (void)hipEventDestroy(e);
   }
 };
@@ -3623,12 +3735,66 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
                       part.d_agg_kind);
 
   HIP_TRY(hipEventRecord(ev0, st));
+  // i64 / f64 comparisons of column ci in WHERE context k, into mk
+  auto cmp_col = [&](hipStream_t s, int ci, int k, uint8_t* mk) {
+    auto& c = plan->cols[ci];
+    for (int pidx : c.cmp_preds) {
+      if (plan->ctx_of(pidx) != k) continue;
+      const auto& pp = plan->preds[pidx];
+      int mode = pp.p.op == GPUQ_BETWEEN ? CMP_RANGE : cmp_mode_of(pp.p.op);
+      if (mode < 0) throw std::runtime_error("bad cmp op");
+      int is_f64 = (c.phys == PT_DOUBLE) ? 1 : 0;
+      int64_t lo = pp.p.i64[0], hi = pp.p.i64[1];
+      if (is_f64) {
+        memcpy(&lo, &pp.p.f64[0], 8);
+        memcpy(&hi, &pp.p.f64[1], 8);
+      }
+      // evaluate only over the row ranges the chunk stats could not prove
+      // (pred_all_true); proven rows keep their memset-1 mask
+      auto rit = part.pred_ranges.find(pidx);
+      if (rit == part.pred_ranges.end()) continue;
+      for (const auto& [row0, nrows] : rit->second)
+        launch_cmp_i64(s, part.d_val[ci] + row0, part.d_valid[ci] + row0,
+                       lo, hi, mode, pp.p.hi_exclusive, is_f64,
+                       mk + row0, nrows);
+    }
+  };
+  // 0. delta fork: behind the memsets above, the side stream
+  // decompresses the early set, delta-decodes the fork columns and evaluates
+  // their comparisons into d_mask, beside the main stream's decompress and
+  // key / value decode. The main stream joins before its first launch that
+  // touches d_mask (mask tasks, row_preds) and in every case before ev1.
+  const bool forked = !part.fork_cols.empty();
+  auto is_fork_col = [&](int ci) {
+    return std::find(part.fork_cols.begin(), part.fork_cols.end(), ci) !=
+           part.fork_cols.end();
+  };
+  if (forked) {
+    hipStream_t sd = part.side;
+    events.fork_side(st, sd);
+    DecompDev E = part.d_early;
+    E.d_raw = part.d_raw;
+    E.d_dec = part.d_dec;
+    E.d_err = part.d_err;
+    launch_decompress(sd, E);
+    for (int ci : part.fork_cols) {
+      auto it = part.tasks.find({TK_DELTA_VAL, ci});
+      if (it != part.tasks.end())
+        launch_delta_i64(sd, part.d_dec, part.d_pages, part.d_ids[it->first],
+                         (int)it->second.size(), part.d_val[ci],
+                         part.d_valid[ci], part.d_err);
+      cmp_col(sd, ci, 0, part.d_mask);
+    }
+    if (plan->exec_dbg)
+      fprintf(stderr, "[gpuq exec] part %d: delta fork cols=%zu\n", (int)pi,
+              part.fork_cols.size());
+  }
   // 1. decompress: parallel segments, then ordered backref resolution
   // (launch_decompress, shared with the test-support entry)
   launch_decompress(st, DecompDev{
       part.d_raw, part.d_dec,
       part.d_segs, (int)part.segs.size(),
-      part.d_seqs, part.d_tiles, (int)part.tiles.size(),
+      part.d_seqs, part.d_tiles, (int)part.tiles.size(), plan->seq_tile_batch,
       part.d_lits_wave, (int)part.lits_wave.size(),
       part.d_res_lane, (int64_t)part.res_lane.size(),
       part.d_res_wave, (int)part.res_wave.size(),
@@ -3644,6 +3810,7 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
       launch_dict_count(st, part.d_dec, part.d_pages, part.d_ids[it->first],
                         (int)it->second.size(), part.d_remap, part.d_table,
                         plan->n_groups, (int)plan->aggs.size(), part.d_err);
+    events.join_side(st);
     HIP_TRY(hipEventRecord(ev1, st));
   } else {
   auto run_task = [&](const std::pair<const std::pair<int, int>,
@@ -3773,6 +3940,14 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
     if (plan->fused_valagg && kv.first.second == plan->valagg_col) continue;
     // mask tasks of the other WHERE contexts run with their OR group below
     if (tk_ctx_of(kv.first.first) != 0) continue;
+    const int kind = tk_kind(kv.first.first);
+    if (forked && kind == TK_DELTA_VAL && is_fork_col(kv.first.second))
+      continue;  // ran on the side stream
+    // value / gid tasks sort before the mask-writing kinds: the join sits
+    // before the first of those
+    if (kind == TK_DICT_MASK || kind == TK_BYTES_CONTAINS ||
+        kind == TK_IS_NULL || kind == TK_IS_NOT_NULL)
+      events.join_side(st);
     run_task(kv, part.d_mask);
   }
   // raw-byte utf8: device hash build assigns dense gids per hash-mode
@@ -3833,32 +4008,14 @@ extern "C" int32_t gpuq_plan_execute(gpuq_plan* plan, int32_t pi,
       }
     }
 
-    // i64 comparisons on decoded arrays
-    for (size_t ci = 0; ci < plan->cols.size(); ci++) {
-      auto& c = plan->cols[ci];
-      for (int pidx : c.cmp_preds) {
-        if (plan->ctx_of(pidx) != k) continue;
-        const auto& pp = plan->preds[pidx];
-        int mode = pp.p.op == GPUQ_BETWEEN ? CMP_RANGE : cmp_mode_of(pp.p.op);
-        if (mode < 0) throw std::runtime_error("bad cmp op");
-        int is_f64 = (c.phys == PT_DOUBLE) ? 1 : 0;
-        int64_t lo = pp.p.i64[0], hi = pp.p.i64[1];
-        if (is_f64) {
-          memcpy(&lo, &pp.p.f64[0], 8);
-          memcpy(&hi, &pp.p.f64[1], 8);
-        }
-        // evaluate only over the row ranges the chunk stats could not prove
-        // (pred_all_true); proven rows keep their memset-1 mask
-        auto rit = part.pred_ranges.find(pidx);
-        if (rit == part.pred_ranges.end()) continue;
-        for (const auto& [row0, nrows] : rit->second)
-          launch_cmp_i64(st, part.d_val[(int)ci] + row0,
-                         part.d_valid[(int)ci] + row0,
-                         lo, hi, mode, pp.p.hi_exclusive, is_f64,
-                         mk + row0, nrows);
-      }
-    }
+    // i64 comparisons on decoded arrays (the fork columns' ran on the side
+    // stream)
+    for (size_t ci = 0; ci < plan->cols.size(); ci++)
+      if (!forked || !is_fork_col((int)ci)) cmp_col(st, (int)ci, k, mk);
   };
+  // the side stream wrote d_mask (plain byte read-modify-writes): nothing on
+  // the main stream touches it before the join
+  events.join_side(st);
   row_preds(0, part.d_mask);
 
   // OR groups (WHERE tree): acc is set to 1 and the first term evaluates
@@ -4527,6 +4684,14 @@ gpuq_plan::~gpuq_plan() {
     for (auto& kv : part.d_gid) F(kv.second);
     for (auto& kv : part.d_val) F(kv.second);
     for (auto& kv : part.d_valid) F(kv.second);
+    const DecompDev& E = part.d_early;
+    for (const void* ptr : {(const void*)E.d_segs, (const void*)E.d_seqs,
+                            (const void*)E.d_tiles, (const void*)E.d_lits_wave,
+                            (const void*)E.d_res_lane, (const void*)E.d_res_wave,
+                            (const void*)E.d_piece_pool, (const void*)E.d_brs,
+                            (const void*)E.d_pagebrs})
+      F(const_cast<void*>(ptr));
+    if (part.side) (void)hipStreamDestroy(part.side);
     if (part.stream) (void)hipStreamDestroy(part.stream);
   }
 }
@@ -4790,6 +4955,7 @@ extern "C" int32_t gpuq_test_decompress(
       d_raw, d_dec,
       B.upload(R.segs), (int)R.segs.size(),
       B.upload(R.seqs), B.upload(R.tiles), (int)R.tiles.size(),
+      seq_tile_batch_env(),   // read per call: one process can run every K
       B.upload(R.lits_wave), (int)R.lits_wave.size(),
       B.upload(R.res_lane), (int64_t)R.res_lane.size(),
       B.upload(R.res_wave), (int)R.res_wave.size(),

@@ -16,6 +16,7 @@
 //    group table fits, flushed once per block with global atomics.
 #include <hip/hip_runtime.h>
 #include <cstring>
+#include <stdexcept>
 #include <rocprim/device/device_radix_sort.hpp>
 #include "dev_types.h"
 #include "like.h"
@@ -254,20 +255,55 @@ k_brres_wave(uint8_t* __restrict__ dec, const DevBrRes* __restrict__ recs,
 }
 
 // litpar sequence tiles (host walk, meta.cpp lz4_walk litpar mode, merged
-// into DevSeq records by plan_decomp_page): one tile per block, one record
-// per thread. A record has no dst — its offset in the tile is the prefix
-// sum of the lengths before it — so the block assembles the tile's whole
-// output span in LDS and flushes it with aligned 16 B stores. The stage is
-// shifted by the destination's misalignment, which keeps the LDS side of
-// the flush body 16 B-aligned too. Only [dst0, dst0 + out_len) is written.
-__global__ void __launch_bounds__(SEQ_TILE_RECS)
-k_seq_tile(const uint8_t* __restrict__ raw, uint8_t* __restrict__ dec,
-           const DevSeq* __restrict__ seqs,
-           const DevSeqTile* __restrict__ tiles, int n) {
-  __shared__ __attribute__((aligned(16))) uint8_t stage[SEQ_TILE_BYTES + 16];
-  __shared__ uint32_t wtot[SEQ_TILE_RECS / WAVE];
-  if (blockIdx.x >= (unsigned)n) return;
-  const DevSeqTile T = tiles[blockIdx.x];
+// into DevSeq records by plan_decomp_page): one record per thread. A record
+// has no dst — its offset in the tile is the prefix sum of the lengths
+// before it — so the block assembles the tile's whole output span in LDS
+// and flushes it with aligned 16 B stores. The stage is shifted by the
+// destination's misalignment, which keeps the LDS side of the flush body
+// 16 B-aligned too. Only [dst0, dst0 + out_len) is written.
+
+// flush one span: bytewise head up to the first 16 B-aligned address, 16 B
+// body, bytewise tail. st[i] holds output byte i and st ≡ o (mod 16).
+__device__ __forceinline__ void seq_flush(uint8_t* __restrict__ o,
+                                          const uint8_t* st, uint32_t out_len,
+                                          uint32_t t) {
+  const uint32_t pad = (uint32_t)((uintptr_t)o & 15);
+  const uint32_t head = min((16u - pad) & 15u, out_len);
+  if (t < head) o[t] = st[t];
+  const uint32_t body = (out_len - head) & ~15u;
+  for (uint32_t i = t * 16u; i < body; i += SEQ_TILE_RECS * 16u)
+    *(uint4*)(o + head + i) = *(const uint4*)(st + head + i);
+  const uint32_t tl = head + body + t;
+  if (tl < out_len) o[tl] = st[tl];
+}
+
+// one record's bytes into the stage at sp; w0 holds its first 8 literal bytes
+__device__ __forceinline__ void seq_put(uint8_t* sp, const uint8_t* s,
+                                        uint64_t w0, uint32_t lit, uint32_t ml,
+                                        uint32_t period, uint64_t pat) {
+  uint64_t w = w0;
+  for (uint32_t k = 0; k < lit; k += 8) {
+    if (k) __builtin_memcpy(&w, s + k, 8);  // tail over-read stays in raw's slack
+    const uint32_t m = min(8u, lit - k);
+    for (uint32_t j = 0; j < m; j++) sp[k + j] = (uint8_t)(w >> (j * 8));
+  }
+  sp += lit;
+  for (uint32_t j = 0, q = 0; j < ml; j++) {
+    sp[j] = (uint8_t)(pat >> (q * 8));
+    if (++q == period) q = 0;
+  }
+}
+
+// one tile per pass of the block. Both barriers are reached by every thread.
+// Back-to-back calls need no barrier in between: the next call writes wtot
+// only after this call's second barrier, behind which nobody reads it, and
+// writes the stage only after its own first barrier, which no thread reaches
+// before it has finished this call's flush.
+__device__ __forceinline__ void seq_tile_one(const uint8_t* __restrict__ raw,
+                                             uint8_t* __restrict__ dec,
+                                             const DevSeq* __restrict__ seqs,
+                                             const DevSeqTile& T,
+                                             uint8_t* stage, uint32_t* wtot) {
   const uint32_t t = threadIdx.x, lane = t & (WAVE - 1);
   const uint32_t out_len = min(T.out_len, SEQ_TILE_BYTES);
   uint8_t* o = dec + T.dst0;
@@ -279,6 +315,11 @@ k_seq_tile(const uint8_t* __restrict__ raw, uint8_t* __restrict__ dec,
   const uint32_t ml = (uint32_t)(R.a >> 49) & 0x1ff;
   const uint32_t period = (uint32_t)(R.a >> 58);
   const uint32_t len = lit + ml;
+  const uint8_t* s = raw + (R.a & ((1ull << 40) - 1));
+  // unconditional (a match-only or absent record reads 8 bytes it ignores,
+  // at its page's start or at raw): no branch between the loads
+  uint64_t w0;
+  __builtin_memcpy(&w0, s, 8);
   // block exclusive scan: wave scan + the wave totals through LDS
   uint32_t incl = len;
 #pragma unroll
@@ -292,32 +333,100 @@ k_seq_tile(const uint8_t* __restrict__ raw, uint8_t* __restrict__ dec,
   for (uint32_t w = 0; w < t / WAVE; w++) off += wtot[w];
 
   // the host checked out_len == sum of the lengths; never leave the stage
-  if (off + len <= out_len) {
-    uint8_t* sp = stage + pad + off;
-    const uint8_t* s = raw + (R.a & ((1ull << 40) - 1));
-    for (uint32_t k = 0; k < lit; k += 8) {
-      uint64_t w;
-      __builtin_memcpy(&w, s + k, 8);   // tail over-read stays in raw's slack
-      const uint32_t m = min(8u, lit - k);
-      for (uint32_t j = 0; j < m; j++) sp[k + j] = (uint8_t)(w >> (j * 8));
-    }
-    sp += lit;
-    for (uint32_t j = 0, q = 0; j < ml; j++) {
-      sp[j] = (uint8_t)(R.pat >> (q * 8));
-      if (++q == period) q = 0;
+  if (off + len <= out_len)
+    seq_put(stage + pad + off, s, w0, lit, ml, period, R.pat);
+  __syncthreads();
+  seq_flush(o, stage + pad, out_len, t);
+}
+
+// K tiles per block: block b takes tiles [bK, min(bK + K, n)) and thread t
+// owns record t of each. The K record loads, and then the K first literal
+// words, are in flight together, so a block keeps K times the bytes moving
+// through the header -> record -> literal chain at the same LDS footprint and
+// wave count. The K sub-stages are packed at 16 B-aligned bases of the one
+// stage, each with its own dst0 & 15 shift. A batch whose spans do not fit
+// the stage together (decided from the headers, so uniformly) runs its tiles
+// one after another.
+template <int K>
+__global__ void __launch_bounds__(SEQ_TILE_RECS)
+k_seq_tile(const uint8_t* __restrict__ raw, uint8_t* __restrict__ dec,
+           const DevSeq* __restrict__ seqs,
+           const DevSeqTile* __restrict__ tiles, int n) {
+  constexpr uint32_t NW = SEQ_TILE_RECS / WAVE;
+  constexpr uint32_t STAGE = SEQ_TILE_BYTES + 16 * K;
+  __shared__ __attribute__((aligned(16))) uint8_t stage[STAGE];
+  __shared__ uint32_t wtot[K][NW];
+  const int64_t b0 = (int64_t)blockIdx.x * K;
+  if (b0 >= n) return;
+  if constexpr (K == 1) {
+    seq_tile_one(raw, dec, seqs, tiles[b0], stage, wtot[0]);
+    return;
+  } else {
+  const uint32_t t = threadIdx.x, lane = t & (WAVE - 1);
+
+  // headers; a slot past the last tile is an empty tile
+  DevSeqTile T[K];
+  uint32_t sbase[K];  // stage index of tile k's output byte 0
+  uint32_t top = 0;
+#pragma unroll
+  for (int k = 0; k < K; k++) {
+    T[k] = b0 + k < n ? tiles[b0 + k] : DevSeqTile{0, 0, 0, 0};
+    T[k].out_len = min(T[k].out_len, SEQ_TILE_BYTES);
+    sbase[k] = top + (uint32_t)((uintptr_t)(dec + T[k].dst0) & 15);
+    top = (sbase[k] + T[k].out_len + 15u) & ~15u;
+  }
+  if (top > STAGE) {
+    for (int k = 0; k < K; k++)
+      if (b0 + k < n) seq_tile_one(raw, dec, seqs, T[k], stage, wtot[0]);
+    return;
+  }
+
+  DevSeq R[K];
+#pragma unroll
+  for (int k = 0; k < K; k++) {
+    R[k] = DevSeq{0, 0};
+    if (t < T[k].n_rec) R[k] = seqs[T[k].rec0 + t];
+  }
+  uint32_t lit[K], ml[K], incl[K];
+  uint64_t w0[K];
+#pragma unroll
+  for (int k = 0; k < K; k++) {
+    lit[k] = (uint32_t)(R[k].a >> 40) & 0x1ff;
+    ml[k] = (uint32_t)(R[k].a >> 49) & 0x1ff;
+    incl[k] = lit[k] + ml[k];
+    // unconditional, so that the K loads issue back to back: a match-only
+    // or absent record reads 8 bytes it ignores, at its page's start or at raw
+    __builtin_memcpy(&w0[k], raw + (R[k].a & ((1ull << 40) - 1)), 8);
+  }
+  // K block exclusive scans on one shuffle ladder, one barrier
+#pragma unroll
+  for (int d = 1; d < WAVE; d <<= 1) {
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+      uint32_t y = __shfl_up(incl[k], d, WAVE);
+      if (lane >= (uint32_t)d) incl[k] += y;
     }
   }
+  if (lane == WAVE - 1) {
+#pragma unroll
+    for (int k = 0; k < K; k++) wtot[k][t / WAVE] = incl[k];
+  }
   __syncthreads();
-
-  // flush: bytewise head up to the first 16 B-aligned address, 16 B body,
-  // bytewise tail (stage index pad + i holds output byte i)
-  const uint32_t head = min((16u - pad) & 15u, out_len);
-  if (t < head) o[t] = stage[pad + t];
-  const uint32_t body = (out_len - head) & ~15u;
-  for (uint32_t i = t * 16u; i < body; i += SEQ_TILE_RECS * 16u)
-    *(uint4*)(o + head + i) = *(const uint4*)(stage + pad + head + i);
-  const uint32_t tl = head + body + t;
-  if (tl < out_len) o[tl] = stage[pad + tl];
+#pragma unroll
+  for (int k = 0; k < K; k++) {
+    const uint32_t len = lit[k] + ml[k];
+    uint32_t off = incl[k] - len;
+    for (uint32_t w = 0; w < t / WAVE; w++) off += wtot[k][w];
+    // the host checked out_len == sum of the lengths; never leave the span
+    if (off + len <= T[k].out_len)
+      seq_put(stage + sbase[k] + off, raw + (R[k].a & ((1ull << 40) - 1)),
+              w0[k], lit[k], ml[k], (uint32_t)(R[k].a >> 58), R[k].pat);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; k++)
+    seq_flush(dec + T[k].dst0, stage + sbase[k], T[k].out_len, t);
+  }
 }
 __global__ void __launch_bounds__(WAVE)
 k_lit_wave(const uint8_t* __restrict__ raw, uint8_t* __restrict__ dec,
@@ -3073,8 +3182,20 @@ void launch_lz4_seg(hipStream_t st, const uint8_t* raw, uint8_t* dec,
   if (n) hipLaunchKernelGGL(k_lz4_seg, dim3(n), dim3(WAVE), 0, st, raw, dec, segs, n, d_err);
 }
 void launch_seq_tile(hipStream_t st, const uint8_t* raw, uint8_t* dec,
-                     const DevSeq* seqs, const DevSeqTile* tiles, int n) {
-  if (n) hipLaunchKernelGGL(k_seq_tile, dim3(n), dim3(SEQ_TILE_RECS), 0, st, raw, dec, seqs, tiles, n);
+                     const DevSeq* seqs, const DevSeqTile* tiles, int n,
+                     int batch) {
+  if (!n) return;
+  auto go = [&](auto kern, int k) {
+    hipLaunchKernelGGL(kern, dim3((n + k - 1) / k), dim3(SEQ_TILE_RECS), 0, st,
+                       raw, dec, seqs, tiles, n);
+  };
+  switch (batch) {
+    case 1: go(k_seq_tile<1>, 1); break;
+    case 2: go(k_seq_tile<2>, 2); break;
+    case 4: go(k_seq_tile<4>, 4); break;
+    case 8: go(k_seq_tile<8>, 8); break;
+    default: throw std::runtime_error("launch_seq_tile: bad batch");
+  }
 }
 void launch_lit_wave(hipStream_t st, const uint8_t* raw, uint8_t* dec,
                      const DevLit* lits, int n) {

@@ -6,8 +6,11 @@
 namespace gpuq {
 void launch_lz4_seg(hipStream_t, const uint8_t* raw, uint8_t* dec,
                     const DevSeg*, int n, int32_t* d_err);
+// batch: tiles per block, 1 | 2 | 4 | 8 (k_seq_tile<K>)
+constexpr int SEQ_TILE_BATCH_DEFAULT = 2;
 void launch_seq_tile(hipStream_t, const uint8_t* raw, uint8_t* dec,
-                     const DevSeq* seqs, const DevSeqTile* tiles, int n);
+                     const DevSeq* seqs, const DevSeqTile* tiles, int n,
+                     int batch);
 void launch_lit_wave(hipStream_t, const uint8_t* raw, uint8_t* dec,
                      const DevLit* lits, int n);
 void launch_lz4_backrefs(hipStream_t, uint8_t* dec, const DevBr*,
